@@ -3,7 +3,12 @@
 cloth_sport_train75 configuration (BASELINE.json configs[1]): batch 256 per GPU, seq_len 50,
 emb_dim 128, hid 32, 1 negative, fp32, item table 2 x 447 410 rows (train_sr.py:450,456), dropout on.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step = the
+milliseconds of one timed step, ...).  --full adds the side measurements behind the timed steps: four more timed windows, per-kernel
+durations and the roofline, the rate with the data pipeline inside the clock, and on cfg2 the gather / scatter stress, the evaluation
+loop and the CPU baseline.  --dump-outputs DIR writes the last timed step's loss and the parameters it left (dump_outputs) as .npy files.
 
 N > 1 either way: under a launcher that has set WORLD_SIZE / RANK / LOCAL_RANK (python -m torch.distributed.run
 --nproc-per-node N bench.py --gpus N ...) this process is one rank; started plainly (python bench.py --gpus N) it
@@ -542,6 +547,40 @@ def cpu_baseline(budget_s=25.0):
                       f"{os.cpu_count()} logical CPUs, {usable_cpus()} usable"}
 
 
+DUMP_TABLE_ROWS = 32768
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(eng, pl, wl, out_dir):
+    """What the timed path hands its caller after its last step, as float32 .npy files: that step's loss and the model's parameters as
+    state_dict() gives them once the pending lazy-Adam moves are applied (flush_table) -- every dense tensor whole, the item table as a
+    fixed seeded sample of rows (3/4 of them among the ids the workload draws, the rest from the other rows; their ids in
+    *.rows_sample_ids.npy, float64).  Returns the file names."""
+    import numpy as np
+    eng.flush_table()
+    eng.sync()
+    g = torch.Generator().manual_seed(0)
+    hi = min(wl["max_id"] + 1, eng.n_rows)
+    live = torch.randperm(hi, generator=g)[: DUMP_TABLE_ROWS * 3 // 4]
+    rest = hi + torch.randperm(eng.n_rows - hi, generator=g)[: DUMP_TABLE_ROWS - len(live)]
+    rows = torch.cat((live, rest)).sort().values
+    table_name = "item_emb_layer.emb_item.weight"
+    arrays = {"loss": pl.loss.detach().float().reshape(-1).cpu().numpy()}
+    for name, v in eng.state_dict().items():
+        if name == table_name:
+            arrays[name + ".rows_sample"] = v.index_select(0, rows.to(v.device)).float().cpu().numpy()
+            arrays[name + ".rows_sample_ids"] = rows.numpy().astype(np.float64)
+        else:
+            arrays[name] = v.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name.replace(os.sep, "_") + ".npy"), a)
+    return sorted(arrays)
+
+
 def self_launch(n: int) -> int:
     """python bench.py --gpus N without a launcher: run `python -m torch.distributed.run --nproc-per-node N bench.py <same args>` as a
     child of this process (which has not touched the GPU: importing torch does not initialise HIP) and relay its output."""
@@ -596,7 +635,17 @@ def main():
     ap.add_argument("--dense-exchange", default="gather", choices=("gather", "allreduce"),
                     help="N > 1: how the flat dense gradient crosses the ranks -- gather: behind the sparse rows in the step's one "
                          "all-gather; allreduce: its own RCCL all-reduce next to it (amid_amd/engine.py DENSE_EXCHANGE)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements behind the timed steps: four more timed windows, per-kernel durations and the "
+                         "roofline, the epoch rate with the data pipeline inside the clock, and for cfg2 the gather / scatter stress, "
+                         "the evaluation loop and the CPU baseline (--no-stress / --no-cpu-baseline drop those)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (dump_outputs); the run then "
+                         "starts its timed steps from the state the warm-up left, whatever the pre-warm did, so that two runs with the "
+                         "same arguments compute the same steps")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))          # rank processes are children; this one never initialises the GPU
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -745,6 +794,9 @@ def main():
     # W untimed warm-up steps, in whole graphs: ceil(W / spg) replays (never fewer than W steps)
     run(-(-args.warmup // spg) * spg)
     barrier()
+    # --dump-outputs: the pre-warm below runs as many steps as fit its wall time; the state the warm-up left is put back behind it, so the
+    # timed steps (and the outputs written after them) are the same steps in every run with these arguments
+    warm = (eng.snapshot(), done) if args.dump_outputs else None
     # pre-warm, not declared in `warmup`: a fresh lease runs its first milliseconds at idle clocks and cold caches, and the driver's
     # --warmup 5 is 2 ms of work; replay whole graphs until PREWARM_MS of wall time have gone by (the same on every rank: the
     # count of replays is agreed on from rank 0's clock), reported as prewarm_ms / prewarm_steps
@@ -761,16 +813,25 @@ def main():
         if not go_on:
             break
     prewarm_ms = (time.perf_counter() - t_pw) * 1e3
+    if warm is not None:
+        eng.restore(warm[0])
+        done = warm[1]
+        warm = None
+        barrier()
     ex0 = dict(exchange.stats) if exchange is not None else None
     dt = window(args.steps)                    # THE timed region: exactly K steps between two barriers
     ex1 = dict(exchange.stats) if exchange is not None else None
-    # four more identical windows behind the headline one (the headline stays window 0): the spread of one 8-ms window on this box
-    windows = [dt] + [window(args.steps) for _ in range(4)]
     loss_last = float(pl.loss.item())
+    dumped = dump_outputs(eng, pl, wl, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    windows = [dt]
+    if args.full:
+        # four more identical windows behind the headline one (the headline stays window 0): the spread of one 8-ms window on this box
+        windows += [window(args.steps) for _ in range(4)]
+        loss_last = float(pl.loss.item())
 
-    # ---- per-kernel durations, measured live with HIP events on the engine's stream (eager launches) ----
+    # ---- --full: per-kernel durations, measured live with HIP events on the engine's stream (eager launches) ----
     roof, kernels = None, {}
-    if rank == 0:
+    if rank == 0 and args.full:
         L = lib()
         n_prof = 20
         L.timer = KernelTimer()
@@ -893,7 +954,7 @@ def main():
     # ---- the same job with the epoch's data pipeline inside the clock: every epoch the loader shuffles, draws fresh negatives
     # (device sampler), packs the epoch and refills the resident pool; then one graph replay per batch (train_sr.py's epoch loop)
     loader_incl = None
-    if use_real and use_pool and use_graph and world == 1 and args.model == "sasrec":
+    if args.full and use_real and use_pool and use_graph and world == 1 and args.model == "sasrec":
         from amid_amd.dataset_seq import DeviceBatches, DualDomainSeqDataset, JointBatches
         dss = [DualDomainSeqDataset.from_tokenised(os.path.join(FIXTURES, f"tok_{n}.npz")) for n in REAL[args.workload]]
         if len(dss) == 2:
@@ -946,10 +1007,12 @@ def main():
                        "parallelism": f"dp{world}"},
             "loss_last": round(loss_last, 6),
             "prewarm_ms": round(prewarm_ms, 1), "prewarm_steps": prewarm_steps,
-            "window_ms_per_step": [round(1e3 * w / args.steps, 4) for w in windows],
-            "roofline": roof,
-            "kernels": kernels,
         }
+        if args.full:
+            out.update(window_ms_per_step=[round(1e3 * w / args.steps, 4) for w in windows], roofline=roof, kernels=kernels)
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped,
+                                     "state": "after the last timed step; the timed steps start from the state the warm-up left"}
         if switches:
             out["config"]["switches"] = {k: str(v) for k, v in switches.items()}          # an A/B line, not the headline
         if loader_incl:
@@ -970,17 +1033,17 @@ def main():
                            # what either dense exchange puts on this rank's receive side per step at this world size
                            "dense_bytes_received_per_step": {"gather": world * dense_bytes, "allreduce": dense_bytes},
                            "padded_unique_rows_per_rank": umax_pool[0]}
-        if world == 1 and args.workload == "cfg2" and args.model == "sasrec" and args.dtype == "f32" and not args.no_stress:
+        if args.full and world == 1 and args.workload == "cfg2" and args.model == "sasrec" and args.dtype == "f32" and not args.no_stress:
             try:
                 out["gather_stress"] = gather_stress(device)
             except Exception as e:              # a side measurement must never cost the headline line
                 out["gather_stress"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.workload == "cfg2" and args.model == "sasrec" and args.dtype == "f32" and not args.no_stress:
+        if args.full and world == 1 and args.workload == "cfg2" and args.model == "sasrec" and args.dtype == "f32" and not args.no_stress:
             try:
                 out["eval"] = eval_throughput(eng, device, Bw, T)
             except Exception as e:
                 out["eval"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu_baseline and world == 1 and args.workload == "cfg2":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "cfg2":
             try:
                 out["cpu_baseline"] = cpu_baseline()
                 out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 1)

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o p -- python3 $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-stress "$@" > $O/bench_under_prof.json 2> $O/prof_err.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o p -- python3 $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-stress "$@" > $O/bench_under_prof.json 2> $O/prof_err.log
 cd $R
 rm -f $O/prof/*kernel_trace.csv
 python3 - $O <<'PY'

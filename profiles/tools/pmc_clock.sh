@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/${1:-pmc_clock}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc -o g -- python3 $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline ${2:---no-graph} > $OUT/bench.json 2> $OUT/err.log
+rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc -o g -- python3 $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline ${2:---no-graph} > $OUT/bench.json 2> $OUT/err.log
 cd $R
 python3 - <<PY
 import csv, glob, collections

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Timing-only ablations of csrc/bert_strip.hip (results are WRONG by construction: only the step time matters): the library relinked
 # with bert_strip.o compiled with -DAMID_BS_ABLATE_PHILOX (keep bits without the Philox rounds) / -DAMID_BS_ABLATE_GELU (no exp / rcp),
-# into profiles/tools/_diag/ (git-ignored); run with AMID_LIB_PATH=<lib> python bench.py --model bert4rec --no-cpu-baseline
+# into profiles/tools/_diag/ (git-ignored); run with AMID_LIB_PATH=<lib> python bench.py --full --model bert4rec --no-cpu-baseline
 set -euo pipefail
 R=$(cd "$(dirname "$0")/../../.." && pwd)
 O=$R/profiles/tools/_diag

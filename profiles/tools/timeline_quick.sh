@@ -9,7 +9,7 @@ shift || true
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d "$O/tl" -o tl -- python3 "$R/bench.py" --steps 60 --warmup 10 --no-cpu-baseline --no-stress "$@" > "$O/b.json" 2> "$O/b.err"
+rocprofv3 --kernel-trace -d "$O/tl" -o tl -- python3 "$R/bench.py" --full --steps 60 --warmup 10 --no-cpu-baseline --no-stress "$@" > "$O/b.json" 2> "$O/b.err"
 cd "$R"
 ANCHOR=step_head
 case " $* " in *" --no-fused-tail "*|*"bert4rec"*|*"--dtype bf16"*) ANCHOR=pack_indices;; esac

@@ -1,11 +1,11 @@
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out/tr
+mkdir -p $R/profiles/tools/_diag/tr
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/tr -o t -- python3 $R/bench.py --steps 40 --warmup 10 --no-cpu-baseline $BENCH_ARGS > $R/gpurun_out/tr/out.json 2> $R/gpurun_out/tr/err.log
+rocprofv3 --kernel-trace --output-format csv -d $R/profiles/tools/_diag/tr -o t -- python3 $R/bench.py --full --steps 40 --warmup 10 --no-cpu-baseline $BENCH_ARGS > $R/profiles/tools/_diag/tr/out.json 2> $R/profiles/tools/_diag/tr/err.log
 cd $R
 python3 - <<'PY'
 import csv, os
-rows = list(csv.DictReader(open("gpurun_out/tr/t_kernel_trace.csv")))
+rows = list(csv.DictReader(open("profiles/tools/_diag/tr/t_kernel_trace.csv")))
 rows = [r for r in rows if "amid" in r["Kernel_Name"] or "copyBuffer" in r["Kernel_Name"]]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # find graph-replay steps: sequences starting with pack_indices; take step #30 (well inside the timed region)
@@ -21,4 +21,4 @@ for r in step:
     print(f"{(s - t0) / 1e3:8.1f} +{(e - s) / 1e3:7.1f}  gap {max(0, s - prev_end) / 1e3:6.1f}  {r['Kernel_Name'][:60]}")
     prev_end = max(prev_end, e)
 PY
-rm -f gpurun_out/tr/t_kernel_trace.csv
+rm -f profiles/tools/_diag/tr/t_kernel_trace.csv

@@ -58,8 +58,8 @@ def test_bench_two_ranks_self_launched_on_one_gpu(dense):
     env = dict(os.environ, AMID_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "4", "--no-cpu-baseline",
-                        "--dense-exchange", dense], env=env, cwd=ROOT, capture_output=True, text=True, timeout=840)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "4", "--full",
+                        "--no-cpu-baseline", "--dense-exchange", dense], env=env, cwd=ROOT, capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -87,3 +87,31 @@ def test_driver_arguments_keep_four_step_graphs():
     assert bench.steps_per_graph_for(4, 10, True) == 2          # K not a multiple: the largest divisor below
     assert bench.steps_per_graph_for(4, 7, True) == 1
     assert bench.steps_per_graph_for(4, 20, False) == 1         # eager / copy input / N > 1: single steps
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain run prints the headline fields only (the side measurements need --full) and --dump-outputs writes the last timed
+    step's loss and parameters as float32 / float64 .npy files within 64 MB."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "4",
+                        "--dump-outputs", str(out_dir)], cwd=ROOT, capture_output=True, text=True, timeout=540)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 8 and out["unit"] == "samples/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["ms_per_step"] > 0 and abs(out["value"] - out["config"]["batch_per_gpu"] * 8 / (8 * out["ms_per_step"] * 1e-3)) < 0.01 * out["value"]
+    for side in ("roofline", "kernels", "window_ms_per_step", "cpu_baseline", "eval", "gather_stress", "samples_per_s_loader_included"):
+        assert side not in out, side
+    files = sorted(os.listdir(out_dir))
+    assert "loss.npy" in files and "item_emb_layer.emb_item.weight.rows_sample.npy" in files and sorted(out["dumped_outputs"]["files"]) == sorted(f[:-4] for f in files)
+    total = 0
+    for f in files:
+        a = np.load(out_dir / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert abs(float(np.load(out_dir / "loss.npy")[0]) - out["loss_last"]) < 1e-5
