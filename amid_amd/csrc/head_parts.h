@@ -352,6 +352,49 @@ __host__ __device__ inline size_t head_lds_floats(int D, int hid) {
     return head_carve_floats(D, hid, 64) + 32 * D;          // scratch: [2][8][2][D] partials of the LayerNorm backward (forward uses half)
 }
 
+// The scorer's three pieces as single-thread functions, for launches that lay the work out differently (full_rank.hip) yet must produce
+// the same bits as the heads below: the same operations in the same order.
+//   user_half_chain: lane `part` of user_half's eight -- sum over e = part, part + 8, ... of w[e ldw] u[e] (w = W1[j][0..D), any stride)
+//   item_half_chain: lane `part` of item_half's eight -- the column quads 4 part + 32 k of the row, w = W1[j][D..2D) (any stride)
+//   head_logit_p:    sigmoid(group_sum<32>(lane j0: w2[j0] relu(au[j0] + ci[j0]) (+ the same for j0 + 32)) + b2) -- scorer_fwd_part's logit,
+//                    the 32-lane tree (pairs, quads, eights, sixteens, halves: balanced, in lane order) unrolled in registers
+// The eight chains are joined by group_sum<8> as the heads do: ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7)).
+__device__ __forceinline__ float user_half_chain(const float* __restrict__ w, int ldw, const float* __restrict__ u, int D, int part) {
+    float acc = 0.f;
+#pragma unroll 8
+    for (int e = part; e < D; e += 8) acc = fmaf(w[e * ldw], u[e], acc);
+    return acc;
+}
+__device__ __forceinline__ float item_half_chain(const float* __restrict__ w, int ldw, const float* __restrict__ row, int D, int part) {
+    float acc = 0.f;
+#pragma unroll 4
+    for (int e = 4 * part; e < D; e += 32) {
+        const float4 it = ld4(row + e);
+        const float* wp = w + e * ldw;
+        acc = fmaf(wp[0], it.x, acc); acc = fmaf(wp[ldw], it.y, acc);
+        acc = fmaf(wp[2 * ldw], it.z, acc); acc = fmaf(wp[3 * ldw], it.w, acc);
+    }
+    return acc;
+}
+template <int HID, class AU, class CI>
+__device__ __forceinline__ float head_logit_p(AU au, CI ci, const float* __restrict__ w2, float b2) {
+    static_assert(HID <= 64, "the heads keep at most two hidden units per lane");
+    float z[32];
+#pragma unroll
+    for (int j0 = 0; j0 < 32; ++j0) {
+        float zp = 0.f;
+        if (j0 < HID) zp = fmaf(w2[j0], fmaxf(au(j0) + ci(j0), 0.f), zp);
+        if (j0 + 32 < HID) zp = fmaf(w2[j0 + 32], fmaxf(au(j0 + 32) + ci(j0 + 32), 0.f), zp);
+        z[j0] = zp;
+    }
+#pragma unroll
+    for (int w = 1; w < 32; w *= 2)
+#pragma unroll
+        for (int i = 0; i < 32; i += 2 * w) z[i] = z[i] + z[i + w];
+    const float zz = z[0] + b2;
+    return 1.0f / (1.0f + expf(-zz));
+}
+
 // au[d][j] = b1[j] + sum_e w1t[e][j] u_d[e].  Eight lanes per output, each summing every eighth e (a thread per output walked D
 // dependent fmas: 2.2 us of the 22 this kernel's workgroup lives -- profiles/tools/head_stamps.py).
 __device__ __forceinline__ void user_half(const HeadArgs& a, const HeadLds& s, const Tg tg) {
@@ -362,11 +405,7 @@ __device__ __forceinline__ void user_half(const HeadArgs& a, const HeadLds& s, c
         const bool on = dj < 2 * hid;
         const int d = on ? dj / hid : 0, j = on ? dj - d * hid : 0;
         float acc = 0.f;
-        if (on) {
-            const float* ur = s.u_s + d * D;
-#pragma unroll 8
-            for (int e = part; e < D; e += 8) acc = fmaf(s.w1t[e * (hid + 1) + j], ur[e], acc);
-        }
+        if (on) acc = user_half_chain(s.w1t + j, hid + 1, s.u_s + d * D, D, part);
         acc = group_sum<8>(acc);
         if (on && part == 0) s.au[dj] = acc + (s.st.b1 != nullptr ? s.st.b1[j] : a.b1[j]);
     }
@@ -383,13 +422,7 @@ __device__ __forceinline__ void item_half(const HeadArgs& a, const HeadLds& s, i
         float acc = 0.f;
         if (on) {
             const float* ir = s.st.items != nullptr ? s.st.items + (n0 + n) * D : a.items + ((long long)b * a.NI + n0 + n) * D;
-#pragma unroll 4
-            for (int e = 4 * part; e < D; e += 32) {
-                const float4 it = ld4(ir + e);
-                const float* wp = s.w1t + (D + e) * (hid + 1) + j;
-                acc = fmaf(wp[0], it.x, acc); acc = fmaf(wp[hid + 1], it.y, acc);
-                acc = fmaf(wp[2 * (hid + 1)], it.z, acc); acc = fmaf(wp[3 * (hid + 1)], it.w, acc);
-            }
+            acc = item_half_chain(s.w1t + D * (hid + 1) + j, hid + 1, ir, D, part);
         }
         acc = group_sum<8>(acc);
         if (on && part == 0) s.ci[n * (hid + 1) + j] = acc;

@@ -1526,6 +1526,67 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
                 out[i].copy_(self._eval_out(pl), non_blocking=True)
         return out
 
+    # ------------------------------------------------------------------ full-catalog evaluation and top-K (csrc/full_rank.hip)
+    # The user vectors come from the launches the sampled evaluation runs for this model (enqueue_eval's LN_last + mean for the plain
+    # SASRec model, enqueue_forward's pl.u otherwise), so the full-catalog scores are the bits test() would give the same candidates.
+    def enqueue_user_vectors(self, pl: SasrecPlan, fix_value: float = 0.0):
+        """The user vectors of the batch loaded into `pl` (load_batch with labels and domain ids), on the engine's stream.  Returns
+        (tensor, dom_stride): user b's vector starts dom_stride * domain[b] + b * D floats into the tensor."""
+        if self.eval_fused_ok(pl):
+            self.enqueue_eval(pl, fix_value, with_loss=False, want_scores=True)
+            return pl.ev_u, 0
+        self.enqueue_prepare(pl, sparse=False)
+        self.enqueue_forward(pl, train=False, with_loss=False)
+        return pl.u, pl.shape.B * self.D
+
+    def _full_rank_workspace(self, B: int, n1: int, n2: int, k: int) -> torch.Tensor:
+        nbytes = int(lib().value("amid_full_rank_workspace_bytes", B, n1, n2, self.hid, k))
+        if nbytes < 0:
+            raise ValueError(f"full rank / top-K: bad sizes B {B}, pools {n1} / {n2}, k {k}")
+        ws = getattr(self, "_fr_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            if ws is not None:
+                ws.record_stream(self.stream)          # (launches still queued on the engine's stream may read the old one)
+            with torch.cuda.stream(self.stream):
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._fr_ws = ws
+        return ws
+
+    def _scorer_ptrs(self):
+        fp = self.dense
+        return (fp.ptr("predictModule.fc.0.weight"), fp.ptr("predictModule.fc.0.bias"), fp.ptr("predictModule.fc.2.weight"),
+                fp.ptr("predictModule.fc.2.bias"))
+
+    def enqueue_full_rank(self, pl: SasrecPlan, pos: torch.Tensor, domain: torch.Tensor, pools, own: Optional[torch.Tensor],
+                          own_off: Optional[torch.Tensor], rows: Optional[torch.Tensor], fix_value: float, rank: torch.Tensor,
+                          rank_raw: torch.Tensor, scores: Optional[torch.Tensor] = None) -> None:
+        """test()'s rank of the positive against the WHOLE pool of its domain minus the row's own items (the set its negatives are drawn
+        from, dataset_seq.py:188 / :206), for the batch loaded into `pl`: rank / rank_raw [B] int32 (with fix_value / with 0).  pos,
+        domain [B] int64; pools (pool_d1, pool_d2) sorted unique int64; own / own_off / rows: DeviceBatches.own, .own_off and the
+        batch's dataset row ids (int32), or None.  scores [B, >= max pool] optional (tests).  Nothing is synchronised."""
+        u, stride = self.enqueue_user_vectors(pl, fix_value)
+        B = pl.shape.B
+        p1, p2 = pools
+        ws = self._full_rank_workspace(B, p1.numel(), p2.numel(), 0)
+        ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
+        lib().call("amid_full_rank_f32", u.data_ptr(), stride, pos.data_ptr(), domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(),
+                   p2.numel(), ptr(own), ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer_ptrs(), self.D, self.hid,
+                   float(fix_value), ws.data_ptr(), pl.err.data_ptr(), rank.data_ptr(), rank_raw.data_ptr(), ptr(scores),
+                   0 if scores is None else scores.shape[1], self.s)
+
+    def enqueue_topk(self, pl: SasrecPlan, domain: torch.Tensor, pools, own: Optional[torch.Tensor], own_off: Optional[torch.Tensor],
+                     rows: Optional[torch.Tensor], k: int, exclude_history: bool, ids: torch.Tensor, scores: torch.Tensor) -> None:
+        """The k best candidates of every row's domain pool (minus its own items with exclude_history) for the batch loaded into `pl`:
+        ids [B, k] int64 / scores [B, k], best first, ties to the lower id, padded with -1 / -inf.  Arguments as enqueue_full_rank."""
+        u, stride = self.enqueue_user_vectors(pl)
+        B = pl.shape.B
+        p1, p2 = pools
+        ws = self._full_rank_workspace(B, p1.numel(), p2.numel(), int(k))
+        ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
+        lib().call("amid_topk_f32", u.data_ptr(), stride, domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel(), ptr(own),
+                   ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer_ptrs(), self.D, self.hid, int(k),
+                   1 if exclude_history else 0, ws.data_ptr(), pl.err.data_ptr(), ids.data_ptr(), scores.data_ptr(), self.s)
+
     # ------------------------------------------------------------------ parameter interchange
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         with torch.no_grad(), torch.cuda.stream(self.stream):

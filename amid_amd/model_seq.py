@@ -317,6 +317,90 @@ class SASRec(nn.Module):
         eng.check_index_error(pl)
         return {"rank": out[:, :B], "rank_raw": out[:, B:2 * B], "loss": out[:, 2 * B:].view(torch.float32).sum(1)}
 
+    def _check_comp_batch(self, B: int) -> None:
+        eng = self.engine
+        bs = eng.itc_bs or eng.inc_bs or getattr(eng, "comp_bs", 0)
+        if bs and B != bs:
+            raise ValueError(f"the batch must hold exactly bs = {bs} rows (trans_bs is Linear(bs, 1) over the batch), got {B}")
+
+    @torch.no_grad()
+    def full_ranks(self, ep: Dict[str, torch.Tensor], batches, fix_value: float) -> Dict[str, torch.Tensor]:
+        """The positive's rank against EVERY candidate its sampled negatives could have been (the domain's pool minus the row's own items,
+        dataset_seq.py:188 / :206) instead of neg_nums of them, by test()'s rule (train_sr.py:114-115): ep = batches.epoch_tensors() of an
+        unshuffled DeviceBatches, whose pools and own sets are used.  Returns device tensors rank / rank_raw [n, B] (int32), shaped like
+        eval_ranks'; the user vectors are the ones the sampled evaluation scores."""
+        eng = self.engine
+        if getattr(batches, "shuffle", True) or not hasattr(batches, "own"):
+            raise ValueError("full_ranks needs the evaluation's unshuffled DeviceBatches (its row order gives the rows' own item sets)")
+        nb, B, T = ep["seq_d1"].shape
+        self._check_comp_batch(B)
+        if eng.table_m is not None:
+            eng.flush_table()
+        neg = ep["neg_samples"].reshape(nb, B, -1)
+        pl = eng.plan(B, T, 1 + neg.shape[2], need_grad=False)
+        dev = eng.device
+        rank = torch.empty(nb, B, dtype=torch.int32, device=dev)
+        rank_raw = torch.empty(nb, B, dtype=torch.int32, device=dev)
+        # the dataset rows of batch i (DeviceBatches.__iter__ without shuffling): (i * world + rank) * bs + 0 .. bs - 1
+        rows = ((torch.arange(nb, device=dev) * batches.world + batches.rank) * B).unsqueeze(1) + torch.arange(B, device=dev)
+        rows = rows.to(torch.int32)
+        pools = (batches.pool[0], batches.pool[1])
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        for i in range(nb):
+            eng.load_batch(pl, ep["i_node"][i], neg[i], ep["seq_d1"][i], ep["seq_d2"][i], ep["label"], ep["domain_id"][i])
+            eng.enqueue_full_rank(pl, ep["i_node"][i], ep["domain_id"][i], pools, batches.own, batches.own_off, rows[i], fix_value, rank[i],
+                                  rank_raw[i])
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(pl)
+        return {"rank": rank, "rank_raw": rank_raw}
+
+    @torch.no_grad()
+    def recommend(self, seq_d1, seq_d2, domain_id, k: int = 10, pool=None, exclude_history: bool = True):
+        """The k items the model scores highest for each user (rows of seq_d1 / seq_d2 [B, T], domain_id [B]: the domain to recommend in),
+        best first, ties to the lower id.  pool: the candidate item ids -- None = every row of the table, a tensor = the same pool for both
+        domains, a pair = (domain 0's, domain 1's).  exclude_history drops the ids of the row's own-domain sequence.  Returns (ids [B, k]
+        int64, scores [B, k] float32) on the device; a row with fewer than k candidates is padded with id -1 and score -inf."""
+        eng = self.engine
+        dev = eng.device
+        seq_d1 = torch.as_tensor(seq_d1).to(dev, torch.int64).contiguous()
+        seq_d2 = torch.as_tensor(seq_d2).to(dev, torch.int64).contiguous()
+        B, T = seq_d1.shape
+        dom = torch.as_tensor(domain_id).to(dev, torch.int64).reshape(B).contiguous()
+        self._check_comp_batch(B)
+        if not 1 <= int(k) <= 256:
+            raise ValueError(f"k must be in 1..256, got {k}")
+        if eng.table_m is not None:
+            eng.flush_table()
+        if pool is None:
+            p = torch.arange(eng.n_rows, dtype=torch.int64, device=dev)
+            pools = (p, p)
+        elif isinstance(pool, (tuple, list)):
+            pools = tuple(torch.unique(torch.as_tensor(q).to(dev, torch.int64)) for q in pool)
+        else:
+            p = torch.unique(torch.as_tensor(pool).to(dev, torch.int64))
+            pools = (p, p)
+        if min(int(q.numel()) for q in pools) < 1:
+            raise ValueError("recommend: an empty candidate pool")
+        # own(b): the sorted unique ids of the row's own-domain sequence, as one CSR list
+        srt = torch.sort(torch.where(dom.unsqueeze(1) != 0, seq_d2, seq_d1), dim=1).values
+        keep = torch.ones_like(srt, dtype=torch.bool)
+        keep[:, 1:] = srt[:, 1:] != srt[:, :-1]
+        own = srt[keep].contiguous()
+        own_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        own_off[1:] = torch.cumsum(keep.sum(1), 0).to(torch.int32)
+        rows = torch.arange(B, dtype=torch.int32, device=dev)
+        zero = torch.zeros(B, dtype=torch.int64, device=dev)
+        label = torch.zeros(B, 2, device=dev)
+        ids = torch.empty(B, int(k), dtype=torch.int64, device=dev)
+        scores = torch.empty(B, int(k), dtype=torch.float32, device=dev)
+        pl = eng.plan(B, T, 2, need_grad=False)
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        eng.load_batch(pl, zero, zero.view(B, 1), seq_d1, seq_d2, label, dom)
+        eng.enqueue_topk(pl, dom, pools, own, own_off, rows, int(k), exclude_history, ids, scores)
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(pl)
+        return ids, scores
+
     def check_indices(self) -> None:
         """Raise IndexError if any batch since the last check carried an item id outside the table (nn.Embedding raises on the spot,
         model_seq.py:27-29; the fused step flags it on the device and keeps going with row 0).  One device -> host read: call it

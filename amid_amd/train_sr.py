@@ -76,6 +76,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_steps", type=int, default=0, help="stop each epoch after this many steps (0 = full epoch)")
     p.add_argument("--dtype", type=str, default="fp32", choices=("fp32", "bf16"),
                    help="fp32: exact fp32 matrix products; bf16: bf16 MFMA operands, fp32 accumulation and storage (sasrec, emb_dim 128)")
+    p.add_argument("--full_rank", action="store_true", help="also rank every positive against its domain's whole item pool (minus the "
+                                                            "user's own items) and log those metrics as d1_full / d2_full")
     return p
 
 
@@ -89,7 +91,7 @@ def test(model, args, val_batches):
     # the plain SASRec model: the whole evaluation set resident in HBM, per batch three launches replayed as one graph -- the own domain's
     # sequence only (the other domain's logits are never read: utils.py:21-40, train_sr.py:63-64), candidates gathered inside the scorer,
     # BCE and both ranks in the same launch (SASRec.eval_ranks); every other model goes through model.forward below
-    fused = None
+    fused, ep, loader = None, None, val_batches
     if hasattr(model, "eval_ranks") and hasattr(val_batches, "epoch_tensors") and len(val_batches) > 0:
         ep = val_batches.epoch_tensors()
         fused = model.eval_ranks(ep, FIX_VALUE)
@@ -121,6 +123,15 @@ def test(model, args, val_batches):
         raw, ov = torch.cat(ranks_raw), torch.cat(ovs)
         out.update(d1_ov=scores_from_ranks(raw[(dom == 0) & (ov == 1)]), d1_no=scores_from_ranks(raw[(dom == 0) & (ov == 0)]),
                    d2_ov=scores_from_ranks(raw[(dom == 1) & (ov == 1)]), d2_no=scores_from_ranks(raw[(dom == 1) & (ov == 0)]))
+    if getattr(args, "full_rank", False) and ep is not None:
+        # the same rows and user vectors against the domain's whole pool minus the row's own items (SASRec.full_ranks)
+        fr = model.full_ranks(ep, loader, FIX_VALUE)
+        rank, dom = fr["rank"].reshape(-1), ep["domain_id"].reshape(-1)
+        out.update(d1_full=scores_from_ranks(rank[dom == 0]), d2_full=scores_from_ranks(rank[dom == 1]))
+        if args.overlap:
+            raw, ov = fr["rank_raw"].reshape(-1), ep["overlap_label"].reshape(-1)
+            out.update(d1_full_ov=scores_from_ranks(raw[(dom == 0) & (ov == 1)]), d1_full_no=scores_from_ranks(raw[(dom == 0) & (ov == 0)]),
+                       d2_full_ov=scores_from_ranks(raw[(dom == 1) & (ov == 1)]), d2_full_no=scores_from_ranks(raw[(dom == 1) & (ov == 0)]))
     return out
 
 
@@ -226,6 +237,8 @@ def main(argv=None):
         parts = args.domain_type.split("+")
         if len(parts) > 2:
             raise SystemExit("-dm takes one dataset or two joined with '+'")
+        if args.full_rank and len(parts) == 2:
+            raise SystemExit(f"--full_rank with a joint job (-dm {args.domain_type}) is not supported: rank one dataset per run")
         trains, vals = [], []
         for j, dm in enumerate(parts):
             ds_train = DualDomainSeqDataset(seq_len=args.seq_len, isTrain=True, neg_nums=args.neg_nums, long_length=args.long_length,

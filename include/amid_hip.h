@@ -1015,6 +1015,29 @@ int amid_eval_head_f32(const float* x, const float* const* ln_w, const float* co
                        int B, int T, int NI, int D, int hid, float eps, float fix_value, float* u, float* p, int* rank, int* rank_raw,
                        float* loss_part, void* stream);
 
+/* ---- full-catalog evaluation and top-K recommendation (csrc/full_rank.hip) -------------------------------------------------------------------
+ * B users against every candidate of their domain's pool (pool_d1 / pool_d2: sorted unique item ids, the sets test()'s negatives are drawn
+ * from, dataset_seq.py:188 / :206) through predictModule: p(u, c) = sigmoid(w2 relu(W1 [u ; table[c]] + b1) + b2), bit-identical to
+ * amid_eval_head_f32 / amid_head_fwd_f32 for the same user vector and row.  User b's vector: u + domain_id[b] * u_dom_stride + b * D (an own-
+ * domain [B, D] tensor: stride 0; the forward's [2, B, D]: stride B * D).  own(b) = own_items[own_off[rows[b]] .. own_off[rows[b] + 1]),
+ * sorted unique per row (DeviceBatches.own / own_off; own_items null: empty).
+ * amid_full_rank_f32: rank[b] = #{c in pool - own(b) : p(u_b, c) > p(u_b, pos[b]) - fix_value}, rank_raw[b] the same with 0 (test()'s rule,
+ * train_sr.py:114-115); scores [B, n_cols] optional: scores[b][i] = p(u_b, pool_dom(b)[i]) (columns past that pool not written).
+ * amid_topk_f32: ids / scores [B, k]: the k best candidates of pool_dom(b) (minus own(b) with exclude_history), best first, ties to the
+ * lower id; fewer than k candidates: id -1, score -inf.  1 <= k <= 256.
+ * Both: D 64 / 128, hid 16 / 32 / 64 (else AMID_ERR_UNSUPPORTED); ids outside [0, n_rows) raise AMID_FLAG_INDEX_RANGE in *flags; workspace:
+ * amid_full_rank_workspace_bytes(B, n_pool_d1, n_pool_d2, hid, k) bytes (k = 0: the rank). */
+long long amid_full_rank_workspace_bytes(int B, int n_pool_d1, int n_pool_d2, int hid, int k);
+int amid_full_rank_f32(const float* u, long long u_dom_stride, const long long* pos, const long long* domain_id, int B,
+                       const long long* pool_d1, int n_pool_d1, const long long* pool_d2, int n_pool_d2, const long long* own_items,
+                       const int* own_off, const int* rows, const float* table, long long n_rows, const float* w1, const float* b1,
+                       const float* w2, const float* b2, int D, int hid, float fix_value, void* workspace, int* flags, int* rank,
+                       int* rank_raw, float* scores, long long n_cols, void* stream);
+int amid_topk_f32(const float* u, long long u_dom_stride, const long long* domain_id, int B, const long long* pool_d1, int n_pool_d1,
+                  const long long* pool_d2, int n_pool_d2, const long long* own_items, const int* own_off, const int* rows,
+                  const float* table, long long n_rows, const float* w1, const float* b1, const float* w2, const float* b2, int D,
+                  int hid, int k, int exclude_history, void* workspace, int* flags, long long* ids, float* scores, void* stream);
+
 /* ---- BERT4Rec strips on bf16 pieces (round 5; csrc/bert_strip.hip MODE 3) ------------------------------------------------------------------
  * The strip launches of a TransformerBlock (model_seq.py:242-245 and its autograd) with every product as six bf16 piece pairs at fp32
  * accuracy -- what SASRec's strips run on since round 4.  Each 128 x 128 weight TILE a chain multiplies with is a three-plane fragment image
