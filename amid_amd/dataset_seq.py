@@ -168,6 +168,15 @@ class DeviceBatches:
                    self.seed, self.epoch, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         return out
 
+    def state_dict(self) -> Dict[str, object]:
+        """The shuffle generator's state and the sampler's epoch counter: restored with load_state_dict(), the next epoch's row order and
+        device-drawn negatives are the ones this loader would give."""
+        return {"gen": self.gen.get_state(), "epoch": int(self.epoch)}
+
+    def load_state_dict(self, sd: Dict[str, object]) -> None:
+        self.gen.set_state(sd["gen"])
+        self.epoch = int(sd["epoch"])
+
     def __len__(self) -> int:
         return len(self.ds) // (self.bs * self.world)                                     # drop_last=True (train_sr.py:452,455)
 
@@ -215,6 +224,13 @@ class JointBatches:
             raise ValueError("joint loaders must agree on batch size, negatives per row, seq_len and pad id")
         self.a, self.b, self.bs, self.k = a, b, a.bs, a.k
         self.device, self.rank, self.world, self.label = a.device, a.rank, a.world, a.label
+
+    def state_dict(self) -> Dict[str, object]:
+        return {"a": self.a.state_dict(), "b": self.b.state_dict()}
+
+    def load_state_dict(self, sd: Dict[str, object]) -> None:
+        self.a.load_state_dict(sd["a"])
+        self.b.load_state_dict(sd["b"])
 
     def __len__(self) -> int:
         return len(self.a) + len(self.b)

@@ -431,6 +431,29 @@ class SASRec(nn.Module):
         self.flush()
         return super().state_dict(*args, **kwargs)
 
+    # -- training state (save / resume) -----------------------------------------------------------
+    TRAINING_STATE_FORMAT = 1
+
+    def save_training_state(self, path, **extra) -> None:
+        """Write what a run needs to go on bit for bit from here (SasrecEngine.training_state: parameters and every Adam state with
+        its raw lazy table state, step counters and dropout seeds) and `extra` -- plain data and tensors, e.g. the epoch and the loaders'
+        state_dict()s -- as torch.save({"format": 1, "engine": ..., "extra": extra}), every tensor on the CPU."""
+        torch.save({"format": self.TRAINING_STATE_FORMAT, "engine": self.engine.training_state(), "extra": extra}, path)
+
+    def load_training_state(self, path) -> dict:
+        """Load a save_training_state() file (or the dict torch.load made of one) into this model, in place, and return its `extra`.
+        The model must have the file's configuration (ValueError naming the first field that differs).  Refused while an epoch pool is
+        installed: the pool's batches are picked by the step counter that the load replaces."""
+        eng = self.engine
+        pl = getattr(self, "_pool_plan", None)
+        if pl is not None and eng.input_pool(pl) is not None:
+            raise ValueError("an epoch pool is installed (begin_epoch_pool): call drop_epoch_pool() before load_training_state()")
+        d = path if isinstance(path, dict) else torch.load(path, map_location="cpu", weights_only=True)
+        if d.get("format") != self.TRAINING_STATE_FORMAT:
+            raise ValueError(f"not a training state of format {self.TRAINING_STATE_FORMAT} (format {d.get('format')!r})")
+        eng.load_training_state(d["engine"])
+        return d.get("extra", {})
+
 
 # ------------------------------------------------------------------------------------------------
 class _GatherFunction(torch.autograd.Function):

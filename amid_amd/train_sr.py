@@ -78,7 +78,136 @@ def build_parser() -> argparse.ArgumentParser:
                    help="fp32: exact fp32 matrix products; bf16: bf16 MFMA operands, fp32 accumulation and storage (sasrec, emb_dim 128)")
     p.add_argument("--full_rank", action="store_true", help="also rank every positive against its domain's whole item pool (minus the "
                                                             "user's own items) and log those metrics as d1_full / d2_full")
+    p.add_argument("--save_dir", type=str, default=None,
+                   help="write DIR/seed{i}/best_d1.pt and best_d2.pt (weights only, kept when MRR_d1 / MRR_d2 >= the best so far; held as "
+                        "device copies until the seed's run ends: two extra table-sized buffers in HBM) and DIR/seed{i}/last.pt (the "
+                        "whole training state, for --resume)")
+    p.add_argument("--save_every", type=int, default=0, help="with --save_dir: write last.pt every N epochs (0: after the seed's last epoch only)")
+    p.add_argument("--resume", type=str, default=None, help="continue the seed of this last.pt at its next epoch, then run the remaining seeds")
     return p
+
+
+# what a last.pt must share with the command line that resumes it
+RESUME_KEYS = ("model", "emb_dim", "seq_len", "hid_dim", "isItC", "isInC", "dtype", "dataset_type", "domain_type", "bs", "overlap_ratio")
+_FLAGS = {"dataset_type": "-ds", "domain_type": "-dm"}
+
+
+def run_signature(args, keys=RESUME_KEYS) -> dict:
+    return {k: getattr(args, k) for k in keys}
+
+
+def read_resume(args, keys=RESUME_KEYS):
+    """--save_dir / --resume, before any GPU work: refused under data parallel; the --resume file (read to the CPU) must come from a
+    run of this command line -- SystemExit naming the first flag that differs.  Returns the file's contents, or None."""
+    if (args.save_dir or args.resume) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--save_dir / --resume are single-GPU only: data-parallel replicas differ in their dropout seeds")
+    if not args.resume:
+        return None
+    ck = torch.load(args.resume, map_location="cpu", weights_only=True)
+    saved = ck.get("extra", {}).get("args", {})
+    for k, v in run_signature(args, keys).items():
+        if saved.get(k) != v:
+            raise SystemExit(f"--resume {args.resume}: {_FLAGS.get(k, '--' + k)} is {v!r} here but {saved.get(k)!r} in the file")
+    return ck
+
+
+def _save_atomic(obj, path: str) -> None:
+    torch.save(obj, path + ".tmp")
+    os.replace(path + ".tmp", path)          # an interrupted write leaves the previous file whole
+
+
+class BestModels:
+    """The reference's best_d1.pt / best_d2.pt (train_sr.py:181-186, :326-332: the model is saved when MRR_d{1,2} >= the best so far)
+    as device-to-device copies of the table and the flat dense buffer -- two spare table-sized buffers in HBM -- written to disk once,
+    when the seed's run ends: an epoch of cloth_sport_train25 with its evaluation takes 0.04 s, a 894 820 x 128 table is 458 MB."""
+
+    def __init__(self, model):
+        self.model, self.copies, self.mrr, self.epoch = model, {}, {}, {}
+
+    def snapshot(self, d: str) -> None:
+        """The model's current weights into domain d's spare buffers (allocated on first use)."""
+        eng = self.model.engine
+        if d not in self.copies:
+            self.copies[d] = (torch.empty_like(eng.table), torch.empty_like(eng.dense.data))
+        eng.flush_table()                 # (the evaluation that judged these weights has flushed already)
+        with torch.cuda.stream(eng.stream):
+            self.copies[d][0].copy_(eng.table)
+            self.copies[d][1].copy_(eng.dense.data)
+
+    def offer(self, res, epoch: int) -> None:
+        for d in ("d1", "d2"):
+            mrr = res[d][6]
+            if mrr >= self.mrr.get(d, 0.0):
+                self.snapshot(d)
+                self.mrr[d], self.epoch[d] = mrr, epoch
+
+    def weights(self, d: str) -> dict:
+        """{state_dict key: CPU fp32 tensor} of domain d's copy (what SASRec.state_dict() gave when it was taken)."""
+        eng = self.model.engine
+        eng.sync()
+        table, data = self.copies[d]
+        with torch.cuda.stream(eng.stream):
+            out = {"item_emb_layer.emb_item.weight": table.to("cpu")}
+            data = data.to("cpu")
+        out.update({n: eng.dense.view(n, data).clone() for n in eng.dense.slots})
+        return out
+
+    def state(self) -> dict:
+        return {d: {"mrr": self.mrr[d], "epoch": self.epoch[d], "weights": self.weights(d)} for d in sorted(self.copies)}
+
+    def load_state(self, st: dict) -> None:
+        eng = self.model.engine
+        for d, s in st.items():
+            self.copies[d] = (torch.empty_like(eng.table), torch.zeros_like(eng.dense.data))
+            torch.cuda.synchronize(eng.device)
+            w = s["weights"]
+            with torch.cuda.stream(eng.stream):
+                self.copies[d][0].copy_(w["item_emb_layer.emb_item.weight"])
+                for n in eng.dense.slots:
+                    eng.dense.view(n, self.copies[d][1]).copy_(w[n])
+            self.mrr[d], self.epoch[d] = s["mrr"], s["epoch"]
+
+    def write(self, out_dir: str) -> None:
+        for d in sorted(self.copies):
+            _save_atomic(self.weights(d), os.path.join(out_dir, f"best_{d}.pt"))
+
+
+class RunFiles:
+    """--save_dir / --save_every / --resume for one seed's run: the best models in HBM (BestModels), last.pt at epoch ends."""
+
+    def __init__(self, args, seed: int, model, loaders: dict, summary: list, keys=RESUME_KEYS):
+        self.args, self.seed, self.model, self.loaders, self.summary, self.keys = args, seed, model, loaders, summary, keys
+        self.dir = os.path.join(args.save_dir, f"seed{seed}") if args.save_dir else None
+        self.best_models = BestModels(model) if self.dir else None
+
+    def resume(self, ck):
+        """Load a last.pt (read_resume's) into the model, the loaders and the best-model copies; returns (next epoch, best)."""
+        extra = self.model.load_training_state(ck)
+        for name, ld in self.loaders.items():
+            ld.load_state_dict(extra["loaders"][name])
+        if self.best_models is not None:
+            self.best_models.load_state(extra["best_models"])
+        return int(extra["epoch"]) + 1, dict(extra["best"])
+
+    def after_eval(self, res, epoch: int) -> None:
+        if self.best_models is not None:
+            self.best_models.offer(res, epoch)
+
+    def end_epoch(self, epoch: int, best: dict, res) -> None:
+        every = self.args.save_every
+        if self.dir is None or not (epoch + 1 == self.args.epoch or (every > 0 and (epoch + 1) % every == 0)):
+            return
+        os.makedirs(self.dir, exist_ok=True)
+        path = os.path.join(self.dir, "last.pt")
+        self.model.save_training_state(path + ".tmp", seed=self.seed, epoch=epoch, best=dict(best), summary=list(self.summary), metrics=res,
+                                       loaders={n: ld.state_dict() for n, ld in self.loaders.items()},
+                                       best_models=self.best_models.state(), args=run_signature(self.args, self.keys))
+        os.replace(path + ".tmp", path)
+
+    def finish(self) -> None:
+        if self.dir is not None:
+            os.makedirs(self.dir, exist_ok=True)
+            self.best_models.write(self.dir)
 
 
 @torch.no_grad()
@@ -135,10 +264,11 @@ def test(model, args, val_batches):
     return out
 
 
-def train(model, train_batches, args, val_batches, exchange=None):
-    """train_sr.py:130-355 with the loop body (:190-217) fused into model.train_step."""
-    best = {}
-    for epoch in range(args.epoch):
+def train(model, train_batches, args, val_batches, exchange=None, start_epoch: int = 0, best=None, files=None):
+    """train_sr.py:130-355 with the loop body (:190-217) fused into model.train_step.  start_epoch / best: where a resumed run goes on
+    (RunFiles.resume); files: the RunFiles of --save_dir."""
+    best = {} if best is None else best
+    for epoch in range(start_epoch, args.epoch):
         stats = AverageMeter("loss", "loss_cls")
         model.train()
         t0, n_samples = time.perf_counter(), 0
@@ -188,6 +318,8 @@ def train(model, train_batches, args, val_batches, exchange=None):
         logger.info(f"epoch {epoch}: {n_samples} samples in {dt:.4f} s = {n_samples / dt:.0f} samples/s (loader included)")
         t1 = time.perf_counter()
         res = test(model, args, val_batches)
+        if files is not None:
+            files.after_eval(res, epoch)
         torch.cuda.synchronize()
         n_eval = len(val_batches) * args.bs
         logger.info(f"epoch {epoch}: evaluated {n_eval} samples x {args.neg_nums + 1} candidates in {time.perf_counter() - t1:.4f} s "
@@ -201,6 +333,8 @@ def train(model, train_batches, args, val_batches, exchange=None):
                 best[(key, n)] = max(best.get((key, n), 0.0), v)
             msg.append(f"val {key} cur/max " + ", ".join(f"{n}: {v:.4f}/{best[(key, n)]:.4f}" for n, v in zip(names, sc)))
         logger.info("\n".join(msg))
+        if files is not None:
+            files.end_epoch(epoch, best, res)
     return best
 
 
@@ -224,9 +358,10 @@ def init_data_parallel(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    ck = read_resume(args)
     rank, world = init_data_parallel(args)
-    summary = []
-    for i in range(args.seeds):
+    summary = list(ck["extra"]["summary"]) if ck is not None else []
+    for i in range(int(ck["extra"]["seed"]) if ck is not None else 0, args.seeds):
         torch.manual_seed(i); np.random.seed(i); random.seed(i)                           # train_sr.py:439-443
         args.log_file = "log" + str(i) + ".txt"
         user_length = 895510                                                              # train_sr.py:447
@@ -281,9 +416,17 @@ def main(argv=None):
             n_idx = args.bs * (2 * args.seq_len + 2)                                      # per-rank index count of a train batch (1 negative)
             exchange = SparseDenseExchange(model.engine.merge_backend(world * n_idx),
                                            host_staging=os.environ.get("AMID_DIST_BACKEND", "nccl") != "nccl")
+        files = RunFiles(args, i, model, {"train": train_batches, "val": val_batches}, summary)
+        start, best = 0, None
+        if ck is not None:
+            start, best = files.resume(ck)
+            ck = None
         init_logger(args.model_dir if rank == 0 else os.path.join(args.model_dir, f"rank{rank}"), args.log_file)
         logger.info(vars(args))
-        best = train(model, train_batches, args, val_batches, exchange)
+        if start:
+            logger.info(f"resumed from {args.resume}: seed {i} at epoch {start}")
+        best = train(model, train_batches, args, val_batches, exchange, start_epoch=start, best=best, files=files)
+        files.finish()
         summary.append(best)
     keys = sorted(summary[0]) if summary else []
     init_logger(args.model_dir if rank == 0 else os.path.join(args.model_dir, f"rank{rank}"), "log_all.txt")

@@ -30,6 +30,7 @@ from .model_seq import BERT4Rec, SASRec
 from .utils import AverageMeter, init_logger
 
 logger = logging.getLogger()
+RESUME_KEYS = base.RESUME_KEYS + ("isDR",)
 
 
 def build_parser():
@@ -40,11 +41,13 @@ def build_parser():
     return p
 
 
-def train(model, train_batches, train_batches_dr, args, val_batches, exchange=None):
-    best = {}
+def train(model, train_batches, train_batches_dr, args, val_batches, exchange=None, start_epoch: int = 0, best=None, files=None):
+    """start_epoch / best / files: as train_sr.train (the best models are the evaluated ones, between the two loops; last.pt is written
+    after the second loop, with both Adam states)."""
+    best = {} if best is None else best
     eng = model.engine
     world = exchange.world if exchange is not None else 1
-    for epoch in range(args.epoch):
+    for epoch in range(start_epoch, args.epoch):
         stats = AverageMeter("loss_cls", "loss_dr_e", "loss_dr_r")
         model.train()
         t0, n_samples = time.perf_counter(), 0
@@ -74,6 +77,8 @@ def train(model, train_batches, train_batches_dr, args, val_batches, exchange=No
         torch.cuda.synchronize()
         t_eval = time.perf_counter()
         res = base.test(model, args, val_batches)
+        if files is not None:
+            files.after_eval(res, epoch)
         torch.cuda.synchronize()
         t_eval = time.perf_counter() - t_eval
         model.train()
@@ -114,6 +119,8 @@ def train(model, train_batches, train_batches_dr, args, val_batches, exchange=No
                 best[(key, n)] = max(best.get((key, n), 0.0), v)
             msg.append(f"val {key} cur/max " + ", ".join(f"{n}: {v:.4f}/{best[(key, n)]:.4f}" for n, v in zip(names, sc)))
         logger.info("\n".join(msg))
+        if files is not None:
+            files.end_epoch(epoch, best, res)
     return best
 
 
@@ -127,12 +134,13 @@ def main(argv=None):
     # one process per GPU under `python -m torch.distributed.run --nproc-per-node N train_sr_dr.py ...` (the reference is single-GPU):
     # --bs is the batch PER GPU, both loops shard their batches by rank and exchange gradients every step (amid_amd/dist.py); with
     # --isItC (run.sh) InterComp's Linear(bs, 1) spans the GLOBAL batch of world x --bs rows (engine._enqueue_user_vectors)
+    ck = base.read_resume(args, RESUME_KEYS)
     rank, world = base.init_data_parallel(args)
     if world > 1 and args.model.lower() != "sasrec":
         raise SystemExit("data-parallel train_sr_dr.py: --model sasrec")
     gbs = args.bs * (world if (args.isItC or args.isInC) else 1)
-    summary = []
-    for i in range(args.seeds):
+    summary = list(ck["extra"]["summary"]) if ck is not None else []
+    for i in range(int(ck["extra"]["seed"]) if ck is not None else 0, args.seeds):
         torch.manual_seed(i); np.random.seed(i); random.seed(i)                           # train_sr_dr.py:624-627
         args.log_file = "log" + str(i) + ".txt"
         user_length, item_length = 895510, 447410                                         # train_sr_dr.py:631-634
@@ -157,9 +165,17 @@ def main(argv=None):
             n_idx = args.bs * (2 * args.seq_len + 2)
             exchange = SparseDenseExchange(model.engine.merge_backend(world * n_idx),
                                            host_staging=os.environ.get("AMID_DIST_BACKEND", "nccl") != "nccl")
+        files = base.RunFiles(args, i, model, {"train": train_batches, "dr": train_batches_dr, "val": val_batches}, summary, RESUME_KEYS)
+        start, best = 0, None
+        if ck is not None:
+            start, best = files.resume(ck)                # (after dr_e_w is set: it is part of the engine's configuration)
+            ck = None
         init_logger(args.model_dir if rank == 0 else os.path.join(args.model_dir, f"rank{rank}"), args.log_file)
         logger.info(vars(args))
-        summary.append(train(model, train_batches, train_batches_dr, args, val_batches, exchange))
+        if start:
+            logger.info(f"resumed from {args.resume}: seed {i} at epoch {start}")
+        summary.append(train(model, train_batches, train_batches_dr, args, val_batches, exchange, start_epoch=start, best=best, files=files))
+        files.finish()
     keys = sorted(summary[0]) if summary else []
     init_logger(args.model_dir if rank == 0 else os.path.join(args.model_dir, f"rank{rank}"), "log_all.txt")
     for k in keys:
