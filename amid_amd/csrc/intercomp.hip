@@ -10,7 +10,7 @@
 //     u_g[b]  = 0.5 mean_t f_g[b,t] + 0.5 c_g
 // Three small kernels: the pair-max per batch row (the only part that needs the full features), and a single-workgroup
 // mix forward / backward over [B, D] means.  Batch-coupled by construction (trans_bs is Linear(bs, 1) over the batch).
-#include "common.h"
+#include "itc_mix_parts.h"
 
 namespace amid {
 
@@ -88,24 +88,7 @@ struct MixArgs {
     int B, D;
 };
 
-__device__ __forceinline__ float block_reduce_sum(float v, float* red) {      // 1024 threads max; all threads get the result
-    v = group_sum<64>(v);
-    __syncthreads();
-    if (lane_id() == 0) red[wave_id()] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += red[k];
-    return s;
-}
-__device__ __forceinline__ float block_reduce_max(float v, float* red) {
-    v = group_max<64>(v);
-    __syncthreads();
-    if (lane_id() == 0) red[wave_id()] = v;
-    __syncthreads();
-    float s = -INFINITY;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s = fmaxf(s, red[k]);
-    return s;
-}
+// (block_reduce_sum / block_reduce_max and the single-thread pieces of the 512-thread forward: itc_mix_parts.h, shared with the evaluation head)
 
 // Both mix kernels run on a grid of `nb` workgroups: the small shared quantities (gate, z, c / dc, dz: a few hundred values that
 // need the whole batch) are recomputed by every workgroup from L2-resident inputs, then each workgroup handles its slice of the
@@ -263,8 +246,7 @@ __global__ __launch_bounds__(1024) void itc_mix_bwd_kernel(const MixArgs a) {
 // ---- fast forms for B <= 256, D <= 128 (the shapes run.sh trains): 512 threads = 16 row groups of 32 lanes, and EVERY global
 // operand of the kernel is requested in its first instructions -- u_raw rows (16 per row group and domain), the W_nn rows, the
 // scores, w_bs -- so the kernel pays one memory latency instead of one per phase (the looped forms above: ~7 dependent phases,
-// 19 / 16 us at B = 256).  Same arithmetic order as the looped forms with 16 row groups.
-constexpr int MIXF_RG = 16, MIXF_K = 16;          // rows per row group: B <= MIXF_RG * MIXF_K; W_nn rows per row group: 2 D / 16 <= 16
+// 19 / 16 us at B = 256).  Same arithmetic order as the looped forms with 16 row groups.  (MIXF_RG, MIXF_K: itc_mix_parts.h)
 
 __global__ __launch_bounds__(512) void itc_mix_fwd_fast_kernel(const MixArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];      // s [B4] | wb [2][B4] | gate [B4] | z [2][D] | c [2][D] | part [16][2 D]
@@ -314,7 +296,7 @@ __global__ __launch_bounds__(512) void itc_mix_fwd_fast_kernel(const MixArgs a) 
     for (int j = threadIdx.x; j < B; j += 512) m = fmaxf(m, s_s[j]);
     m = block_reduce_max(m, red);
     float l = 0.f, sw[2] = {0.f, 0.f};
-    for (int j = threadIdx.x; j < B; j += 512) { l += expf(s_s[j] - m); sw[0] += wb_s[j]; sw[1] += wb_s[B4 + j]; }
+    for (int j = threadIdx.x; j < B; j += 512) { l += itc_softmax_term(s_s[j], m); sw[0] += wb_s[j]; sw[1] += wb_s[B4 + j]; }
     {   // the three sums through ONE pair of barriers
         __shared__ float red3[3][8];
         l = group_sum<64>(l); sw[0] = group_sum<64>(sw[0]); sw[1] = group_sum<64>(sw[1]);
@@ -325,7 +307,7 @@ __global__ __launch_bounds__(512) void itc_mix_fwd_fast_kernel(const MixArgs a) 
         for (int k = 0; k < 8; ++k) { l += red3[0][k]; sw[0] += red3[1][k]; sw[1] += red3[2][k]; }
     }
     for (int j = threadIdx.x; j < B; j += 512) {
-        const float gt = (expf(s_s[j] - m) / l > a.threshold) ? 1.f : 0.f;
+        const float gt = itc_gate(s_s[j], m, l, a.threshold);
         gate_s[j] = gt;
         if (first) a.gate[j] = gt;
     }
@@ -339,8 +321,7 @@ __global__ __launch_bounds__(512) void itc_mix_fwd_fast_kernel(const MixArgs a) 
         for (int k = 0; k < MIXF_K; ++k) {
             const int j = rg + k * MIXF_RG;
             const float w = (j < B) ? wb_s[g * B4 + j] * gate_s[j] : 0.f;
-            acc.x = fmaf(w, uv[g][k].x, acc.x); acc.y = fmaf(w, uv[g][k].y, acc.y);
-            acc.z = fmaf(w, uv[g][k].z, acc.z); acc.w = fmaf(w, uv[g][k].w, acc.w);
+            itc_z_step(acc, w, uv[g][k]);
         }
         if (on) st4(part + rg * 2 * D + g * D + 4 * sub, acc);
     }
@@ -362,7 +343,7 @@ __global__ __launch_bounds__(512) void itc_mix_fwd_fast_kernel(const MixArgs a) 
         for (int k = 0; k < MIXF_K; ++k) {
             const int r = rg + k * MIXF_RG;
             const float4 z4 = on ? ld4(z_s + ((r >= D) ? D : 0) + 4 * sub) : make_float4(0.f, 0.f, 0.f, 0.f);
-            v[k] = fmaf(wv[k].x, z4.x, fmaf(wv[k].y, z4.y, fmaf(wv[k].z, z4.z, wv[k].w * z4.w)));
+            v[k] = itc_c_dot4(wv[k], z4);
         }
 #pragma unroll
         for (int half = 8, bit = 16; half >= 1; half >>= 1, bit >>= 1) {      // xor 16, 8, 4, 2: keep `half` rows, send the other half
@@ -379,7 +360,7 @@ __global__ __launch_bounds__(512) void itc_mix_fwd_fast_kernel(const MixArgs a) 
         const int r = rg + kk * MIXF_RG;
         if ((sub & 1) == 0 && r < 2 * D) {
             const int g = (r >= D) ? 1 : 0, o = r - g * D;
-            c_s[r] = v[0] + a.bnn[g][o] * sw[g] + (g ? bias_bs1 : bias_bs0);
+            c_s[r] = itc_c_finish(v[0], a.bnn[g][o], sw[g], g ? bias_bs1 : bias_bs0);
         }
     }
     __syncthreads();
@@ -388,8 +369,8 @@ __global__ __launch_bounds__(512) void itc_mix_fwd_fast_kernel(const MixArgs a) 
         const int i = threadIdx.x, b = b0 + i / q, c4 = 4 * (i % q);
         if (b < b1) {
             const float4 cc = ld4(c_s + g * D + c4);
-            st4(a.u_mix + ((long long)g * B + b) * D + c4, make_float4(0.5f * own[g].x + 0.5f * cc.x, 0.5f * own[g].y + 0.5f * cc.y,
-                                                                     0.5f * own[g].z + 0.5f * cc.z, 0.5f * own[g].w + 0.5f * cc.w));
+            st4(a.u_mix + ((long long)g * B + b) * D + c4, make_float4(itc_mix(own[g].x, cc.x), itc_mix(own[g].y, cc.y),
+                                                                     itc_mix(own[g].z, cc.z), itc_mix(own[g].w, cc.w)));
         }
     }
 }

@@ -596,11 +596,12 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         return bool(self._ceff() != "bf16" and self.FWD_SPLIT and self.D == 128 and pl.strip and self.SEQ_FORWARD and not self.inc_bs
                     and lib().value("amid_sas_seq_supported", B, T, self.D, self.H))
 
-    def _enqueue_k1(self, pl: SasrecPlan, pos0, pos1, tmq, tr: int, p_drop: float, lf) -> None:
+    def _enqueue_k1(self, pl: SasrecPlan, pos0, pos1, tmq, tr: int, p_drop: float, lf, items: bool = True) -> None:
         """The gather K1 of a forward in the variant the step needs: over every sequence or the live list `lf`, writing the compact index
-        list, with the folded catch-up (+ phase 1 of a riding sort)."""
+        list, with the folded catch-up (+ phase 1 of a riding sort).  items=False: the sequences' rows only (the evaluation head gathers
+        the candidates' rows itself)."""
         L, s, shp, D = lib(), self.s, pl.shape, self.D
-        B, T, NI = shp.B, shp.Tenc, shp.NI
+        B, T, NI = shp.B, shp.Tenc, shp.NI if items else 0
         st = self.step_state.data_ptr()
         # what this launch's riders write is decided HERE: a flag left by an earlier forward (e.g. a train-mode forward without a backward)
         # must not make the next backward skip its images
@@ -658,7 +659,9 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         lib().call("amid_lazy_adam_catchup_positions_f32", self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(),
                    self.table_last.data_ptr(), pl.idx_all.data_ptr(), pl.shape.n_idx, self.D, self.step_state.data_ptr(), self.s)
 
-    def enqueue_forward(self, pl: SasrecPlan, train: bool, with_loss: bool, sum_loss: bool = True) -> None:
+    def enqueue_forward(self, pl: SasrecPlan, train: bool, with_loss: bool, sum_loss: bool = True, head: bool = True, gather_items: bool = True) -> None:
+        """head=False: stop behind the encoders (pl.x[2] is the last layer's output); gather_items=False: the candidates' rows are not gathered
+        (enqueue_eval: its head reads them from the table)."""
         L, s, shp, D = lib(), self.s, pl.shape, self.D
         B, T, NI, M = shp.B, shp.Tenc, shp.NI, shp.M
         st = self.step_state.data_ptr()
@@ -675,7 +678,8 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         if lv is not None and not getattr(pl, "live_packed", False):
             L.call("amid_live_list_i32", pl.domain.data_ptr(), B, pl.live.data_ptr(), s)
         if self.inc_bs:      # plain gather, InnerComp's token group, then the 2T-token encoder input (csrc/innercomp.hip)
-            L.call("amid_gather_rows_f32", self.table.data_ptr(), self.n_rows, D, pl.idx_all.data_ptr(), 0, shp.n_idx, pl.xg.data_ptr(), None, s)
+            L.call("amid_gather_rows_f32", self.table.data_ptr(), self.n_rows, D, pl.idx_all.data_ptr(), 0, shp.n_idx if gather_items else 2 * shp.Mi,
+                   pl.xg.data_ptr(), None, s)
             L.call("amid_inc_score_f32", pl.xg.data_ptr(), B, shp.T, D, pl.inc_s.data_ptr(), s)
             wts = (self._pp("inc_d{d}.trans_nn.weight"), self._pp("inc_d{d}.trans_nn.bias"), self._pp("inc_d{d}.trans_bs.weight"),
                    self._pp("inc_d{d}.trans_bs.bias"))
@@ -702,7 +706,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             if gat:                                     # the forward's workgroups gather their own rows; the step head wrote the images
                 pl.w16_written = pl.wT16x3_written = True
             else:
-                self._enqueue_k1(pl, fp.ptr("sac1.pos_emb.weight"), fp.ptr("sac2.pos_emb.weight"), pl.tmq.data_ptr(), tr, SASREC_P_DROP, lf)
+                self._enqueue_k1(pl, fp.ptr("sac1.pos_emb.weight"), fp.ptr("sac2.pos_emb.weight"), pl.tmq.data_ptr(), tr, SASREC_P_DROP, lf, gather_items)
         def layer_ptrs(l):
             pre = f"sac{{d}}"
             return ((self._pp(f"{pre}.attention_layernorms.{l}.weight"), self._pp(f"{pre}.attention_layernorms.{l}.bias"),
@@ -806,6 +810,10 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
                     L.call("amid_sas_oproj_ffn_fwd_f32" + pl.rt_suffix, pl.o[l].data_ptr(), pl.qn[l].data_ptr(), *rest, pl.tmq.data_ptr(), SASREC_LN_EPS, M, D,
                            pl.rpt, l, st, tr, SASREC_P_DROP, pl.r[l].data_ptr(), pl.y[l].data_ptr(), pl.h[l].data_ptr(), pl.x[l + 1].data_ptr(),
                            self.mma_bf16, s)
+        if not head:
+            return
+        if not gather_items:
+            raise ValueError("enqueue_forward: the heads read the candidates' gathered rows (gather_items=False goes with head=False)")
         items = pl.xg.data_ptr() + 4 * 2 * shp.Mi * D
         if (self.dr or self.itc_bs) and getattr(self, "_fuse_scorers", False) and with_loss and not sum_loss:
             self._enqueue_user_vectors(pl)           # train step: the scorers run as ONE forward + loss + backward launch in enqueue_backward
@@ -830,8 +838,9 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             L.call("amid_sum_vector_f32", pl.loss_part.data_ptr(), B, pl.loss.data_ptr(), s)
 
     # ---- isItC head: last LayerNorm + mean -> pair-max -> batch-softmax gate + mix -> scorer (csrc/intercomp.hip) ----
-    def _enqueue_user_vectors(self, pl: SasrecPlan) -> None:
-        """pl.u [2, B, D]: mean over time of the last LayerNorm (:385, :432-434), mixed with the InterComp group when isItC."""
+    def _enqueue_user_vectors(self, pl: SasrecPlan, mix: bool = True) -> None:
+        """pl.u [2, B, D]: mean over time of the last LayerNorm (:385, :432-434), mixed with the InterComp group when isItC
+        (mix=False: only the pair-max launch -- pl.itc_s and the unmixed pl.u_raw; the evaluation head mixes in its prologue)."""
         L, s, shp, D = lib(), self.s, pl.shape, self.D
         B, T = shp.B, shp.Tenc
         fp = self.dense
@@ -841,6 +850,8 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         else:            # the pair-max kernel has every LayerNorm'd row of (b) in LDS: it emits the means too
             L.call("amid_itc_pairmax_f32", pl.x[2].data_ptr(), self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"),
                    B, T, D, SASREC_LN_EPS, pl.itc_s.data_ptr(), pl.u_raw.data_ptr(), s)
+            if not mix:
+                return
             u_raw, itc_s, u_out, Bm = pl.u_raw, pl.itc_s, pl.u, B
             if pl.itc_world > 1:
                 # data parallel: the module couples the rows of the GLOBAL batch (softmax over the batch model_seq.py:491, Linear(bs, 1)
@@ -1399,12 +1410,28 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
     # head gathers them), the inference forward over the live sequences (nothing saved), amid_eval_head_f32 (LN_last + mean, the scorer over
     # the 1 + neg_nums candidates, masked BCE, the positive's rank).  test() reads only the own domain's logits of a sample (utils.py:21-40)
     # and masks the other domain's loss terms (train_sr.py:63-64), so nothing else is computed; model.forward keeps returning both.
+    # The isDR / isItC / isInC models (one GPU, the whole bs-row batch in the plan) keep the launches their forward forms the user vectors
+    # with -- the bits of enqueue_forward(train=False) -- and gain the head: no [B, NI, D] copy of the candidates' rows, BCE and ranks in the
+    # scorer's launch, one graph replay a batch.
+    #   isDR:   the plain model's marshal + forward over the live sequences, amid_lnmean_fwd_f32 (this model's LN_last + mean: its own
+    #           kernel, compiled apart from the fused head's, so its vector is READ), amid_eval_head_u_f32.  predict_ips / predict_gfunc
+    #           are not evaluated: test() reads outs[0], outs[1] only.
+    #   isItC:  marshal, K1 over BOTH domains' sequences (the group token is built from every row's other-domain features), the inference
+    #           forward with a null live list, amid_itc_pairmax_f32 (s, u_raw), amid_eval_head_u_f32 with the mix as its prologue (32 .. 256
+    #           rows, D 64 / 128: five launches; other batches: amid_itc_mix_fwd_f32 in front of it, the head reading pl.u).
+    #   isInC:  marshal + enqueue_forward's own gather / token group / encoder launches over the 2T-token rows (gather_items=False,
+    #           head=False), then amid_eval_head_f32 on pl.x[2] (+ isDR: amid_lnmean_fwd_f32 and amid_eval_head_u_f32).
     EVAL_FUSED = True
 
     def eval_fused_ok(self, pl: SasrecPlan) -> bool:
-        return bool(self.EVAL_FUSED and not self.itc_bs and not self.inc_bs and not self.dr and not getattr(self, "comp", "") and pl.strip
-                    and self.SEQ_FORWARD and self.input_pool(pl) is None
-                    and lib().value("amid_sas_seq_supported", pl.shape.B, pl.shape.Tenc, self.D, self.H))
+        shp = pl.shape
+        if not self.EVAL_FUSED or getattr(self, "comp", "") or self.input_pool(pl) is not None:
+            return False
+        if getattr(pl, "itc_world", 1) != 1 or getattr(pl, "inc_world", 1) != 1:      # a data-parallel shard of a comp batch keeps enqueue_forward
+            return False
+        if self.inc_bs:          # the encoders are enqueue_forward's for any shape; the head's own limits (amid_eval_head_f32)
+            return bool(self.D % 32 == 0 and self.D <= 128 and 0 < self.hid <= 64 and self.hid % 4 == 0)
+        return bool(pl.strip and self.SEQ_FORWARD and lib().value("amid_sas_seq_supported", shp.B, shp.Tenc, self.D, self.H))
 
     def _eval_out(self, pl: SasrecPlan):
         """The batch's results, one int32 image [rank B | rank_raw B | loss_part B (fp32 bits)] (+ the scores, for tests)."""
@@ -1425,15 +1452,45 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             raise ValueError("enqueue_eval: this model / shape evaluates through enqueue_forward (eval_fused_ok)")
         L, s, shp, D = lib(), self.s, pl.shape, self.D
         B, T, NI = shp.B, shp.Tenc, shp.NI
-        fp, st = self.dense, self.step_state.data_ptr()
         self._eval_out(pl)
         L.call("amid_pack_indices_live", pl.in_i_node.data_ptr(), pl.in_neg.data_ptr(), pl.in_seq_d1.data_ptr(), pl.in_seq_d2.data_ptr(),
                B, shp.T, NI - 1, self.n_rows, pl.idx_all.data_ptr(), pl.err.data_ptr(), None, pl.domain.data_ptr(), pl.live.data_ptr(), s)
-        lf = pl.live.data_ptr()
+        if self.inc_bs:           # enqueue_forward's launches up to the last encoder layer, the sequences' rows only
+            self.enqueue_forward(pl, train=False, with_loss=False, head=False, gather_items=False)
+        else:
+            self._enqueue_eval_encoders(pl, build_images)
+        ids = pl.idx_all.data_ptr() + 4 * 2 * shp.Mi
+        outs = (pl.ev_u.data_ptr() if want_scores else None, pl.ev_p.data_ptr() if want_scores else None, pl.ev_rank.data_ptr(),
+                pl.ev_rank_raw.data_ptr(), pl.ev_loss_part.data_ptr() if with_loss else None, s)
+        if self.dr or self.itc_bs:       # the user vectors by this model's own launches (pl.u [2, B, D]), read by the head
+            # isItC at the batch sizes amid_itc_mix_fwd_f32 runs its 512-thread form on: the mix is the head's prologue, from pl.u_raw
+            fold = bool(self.itc_bs and 32 <= B <= 256 and D in (64, 128))
+            self._enqueue_user_vectors(pl, mix=not fold)
+            mixargs = (None,) * 5 + (0.0, None)
+            if fold:
+                mixargs = (pl.itc_s.data_ptr(), self._pp("itc_d{d}.trans_nn.weight"), self._pp("itc_d{d}.trans_nn.bias"),
+                           self._pp("itc_d{d}.trans_bs.weight"), self._pp("itc_d{d}.trans_bs.bias"), self.itc_threshold, pl.itc_gate.data_ptr())
+            L.call("amid_eval_head_u_f32", (pl.u_raw if fold else pl.u).data_ptr(), B * D, self.table.data_ptr(), ids, *self._scorer_ptrs(),
+                   pl.labels.data_ptr() if with_loss else None, pl.domain.data_ptr(), B, NI, D, self.hid, float(fix_value), *outs[:-1],
+                   *mixargs, s)
+            return
+        L.call("amid_eval_head_f32", pl.x[2].data_ptr(), self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"),
+               self.table.data_ptr(), ids, *self._scorer_ptrs(), pl.labels.data_ptr() if with_loss else None, pl.domain.data_ptr(), B, T, NI, D,
+               self.hid, SASREC_LN_EPS, float(fix_value), *outs)
+
+    def _enqueue_eval_encoders(self, pl: SasrecPlan, build_images: bool) -> None:
+        """The sequences' rows and the inference forward of an evaluation batch, up to pl.x[2]: over the live list, or (a null list) over both
+        domains of every row for a model whose head needs them.  The kernels are enqueue_forward(train=False)'s for the shape, or their
+        inference twins (tests/test_gpu_eval.py)."""
+        L, s, shp, D = lib(), self.s, pl.shape, self.D
+        B, T = shp.B, shp.Tenc
+        fp, st = self.dense, self.step_state.data_ptr()
+        lf = None if self.itc_bs else pl.live.data_ptr()      # isItC: the pair-max reads both domains' rows of every sample
         pos = (fp.ptr("sac1.pos_emb.weight"), fp.ptr("sac2.pos_emb.weight"))
         split = self._fwd_on_pieces(pl, B, T)
         pl.w16_written = pl.wT16x3_written = False
-        gat = bool(split and self.GATHER_ON_FWD)          # the forward's workgroups gather their own rows: three launches a batch
+        # the forward's workgroups gather their own rows: three launches a batch (the gather prologue walks a live list: not without one)
+        gat = bool(split and self.GATHER_ON_FWD and lf is not None)
         if gat:
             src, w16 = self._w16_images(3)
             if build_images:
@@ -1445,8 +1502,12 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         else:
             if split:
                 src, w16 = self._w16_images(3)
-            L.call("amid_embed_fwd_live_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), *pos, B, T, D, 0, pl.xg.data_ptr(), pl.tmq.data_ptr(),
-                   st, 0, SASREC_P_DROP, lf, s)
+            if lf is not None:
+                L.call("amid_embed_fwd_live_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), *pos, B, T, D, 0, pl.xg.data_ptr(),
+                       pl.tmq.data_ptr(), st, 0, SASREC_P_DROP, lf, s)
+            else:
+                L.call("amid_embed_fwd_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), *pos, B, T, D, 0, pl.xg.data_ptr(), pl.tmq.data_ptr(),
+                       st, 0, SASREC_P_DROP, s)
         fam = lambda fmt: ptr_array([fp.ptr(fmt.format(d=d, l=l)) for l in (0, 1) for d in (1, 2)])      # noqa: E731  [layer][domain]
         key = ("eval_fwd", id(pl))
         c = self._ptr_cache.get(key)
@@ -1475,12 +1536,6 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             else:
                 L.call("amid_sas_seq_fwd_f32", 2, tl(pl.x[:2]), pl.x[2].data_ptr(), *c, *saved, pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, self.H,
                        lf, st, 0, SASREC_P_DROP, s)
-        L.call("amid_eval_head_f32", pl.x[2].data_ptr(), self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"),
-               self.table.data_ptr(), pl.idx_all.data_ptr() + 4 * 2 * shp.Mi, fp.ptr("predictModule.fc.0.weight"),
-               fp.ptr("predictModule.fc.0.bias"), fp.ptr("predictModule.fc.2.weight"), fp.ptr("predictModule.fc.2.bias"),
-               pl.labels.data_ptr() if with_loss else None, pl.domain.data_ptr(), B, T, NI, D, self.hid, SASREC_LN_EPS, float(fix_value),
-               pl.ev_u.data_ptr() if want_scores else None, pl.ev_p.data_ptr() if want_scores else None, pl.ev_rank.data_ptr(),
-               pl.ev_rank_raw.data_ptr(), pl.ev_loss_part.data_ptr() if with_loss else None, s)
 
     def capture_eval(self, pl: SasrecPlan, fix_value: float, with_loss: bool = True) -> None:
         """The evaluation batch as a hipGraph over the plan's static inputs (parameters are read at replay time and the forward's weight
@@ -1527,8 +1582,9 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         return out
 
     # ------------------------------------------------------------------ full-catalog evaluation and top-K (csrc/full_rank.hip)
-    # The user vectors come from the launches the sampled evaluation runs for this model (enqueue_eval's LN_last + mean for the plain
-    # SASRec model, enqueue_forward's pl.u otherwise), so the full-catalog scores are the bits test() would give the same candidates.
+    # The user vectors come from the launches the sampled evaluation runs for this model (enqueue_eval's own-domain pl.ev_u -- for isItC
+    # the mixed vector --, enqueue_forward's pl.u where eval_fused_ok says no), so the full-catalog scores are the bits test() would give the
+    # same candidates.
     def enqueue_user_vectors(self, pl: SasrecPlan, fix_value: float = 0.0):
         """The user vectors of the batch loaded into `pl` (load_batch with labels and domain ids), on the engine's stream.  Returns
         (tensor, dom_stride): user b's vector starts dom_stride * domain[b] + b * D floats into the tensor."""

@@ -301,8 +301,10 @@ class SASRec(nn.Module):
         """test()'s arithmetic (train_sr.py:31-128) over a whole evaluation set resident in HBM (ep = DeviceBatches.epoch_tensors()):
         per batch the eval-mode forward of every sample's OWN domain sequence, its 1 + neg_nums scores, the masked BCE mean (:63-64) and
         the positive's rank with and without fix_value (:114-115; utils.py:21-40, :296-297) -- three launches replayed as one graph
-        (SasrecEngine.enqueue_eval).  Returns device tensors rank [n, B], rank_raw [n, B] (int32) and loss [n], or None when this model
-        evaluates through forward() (isItC / isInC / isDR, BERT4Rec, shapes the one-launch forward does not cover)."""
+        (SasrecEngine.enqueue_eval; isDR / isItC / isInC models: the launches their forward forms the user vectors with, both domains'
+        sequences where a comp module needs them, and the same scorer launch).  Returns device tensors rank [n, B], rank_raw [n, B]
+        (int32) and loss [n], or None when this model evaluates through forward() (BERT4Rec, shapes the engine's evaluation does not cover,
+        a comp model whose batch is not its bs rows: forward() then raises what it always raised)."""
         eng = self.engine
         nb, B, T = ep["seq_d1"].shape
         neg = ep["neg_samples"].reshape(nb, B, -1)

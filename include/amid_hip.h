@@ -1014,6 +1014,22 @@ int amid_eval_head_f32(const float* x, const float* const* ln_w, const float* co
                        const float* w1, const float* b1, const float* w2, const float* b2, const float* labels, const long long* domain_id,
                        int B, int T, int NI, int D, int hid, float eps, float fix_value, float* u, float* p, int* rank, int* rank_raw,
                        float* loss_part, void* stream);
+/* amid_eval_head_u_f32: the same head on GIVEN user vectors, for the models whose forward forms them in launches of their own (isDR:
+ * amid_lnmean_fwd_f32; isItC: amid_itc_pairmax_f32 + amid_itc_mix_fwd_f32): user b's vector is read at u_src + u_dom_stride * (domain_id[b]
+ * != 0) + b * D (the forward's [2, B, D]: stride B * D; an own-domain [B, D]: stride 0) where amid_eval_head_f32 computes LN_last + mean;
+ * everything behind it -- the candidates' rows gathered in the launch, the scorer, BCE terms, both ranks, the optional u [B, D] (a copy of the
+ * vectors scored; must not alias u_src) and p [B, NI] -- is the same code: the bits of amid_scorer_fwd_f32 + amid_positive_rank_f32 on the
+ * same vectors.
+ * itc_s != NULL folds InterComp's mix into the launch: u_src is then the UNMIXED u_raw [2, B, D] of amid_itc_pairmax_f32 (u_dom_stride = B * D),
+ * itc_s its scores [B], w_nn / b_nn / w_bs / b_bs host arrays of 2 device pointers (itc_d1, itc_d2), and every workgroup recomputes the
+ * thresholded batch softmax, z_g and c_g of its sample's domain and scores u = 0.5 u_raw[g][b] + 0.5 c_g: the bits amid_itc_mix_fwd_f32 writes
+ * (its 512-thread form's operations in its order, csrc/itc_mix_parts.h).  32 <= B <= 256 and D 64 / 128 only (AMID_ERR_UNSUPPORTED otherwise:
+ * run amid_itc_mix_fwd_f32 and pass its output); gate [B] optional (the batch's gates).  itc_s == NULL: the five mix arguments must be NULL. */
+int amid_eval_head_u_f32(const float* u_src, long long u_dom_stride, const float* table, const int* ids, const float* w1, const float* b1,
+                         const float* w2, const float* b2, const float* labels, const long long* domain_id, int B, int NI, int D, int hid,
+                         float fix_value, float* u, float* p, int* rank, int* rank_raw, float* loss_part, const float* itc_s,
+                         const float* const* w_nn, const float* const* b_nn, const float* const* w_bs, const float* const* b_bs,
+                         float threshold, float* gate, void* stream);
 
 /* ---- full-catalog evaluation and top-K recommendation (csrc/full_rank.hip) -------------------------------------------------------------------
  * B users against every candidate of their domain's pool (pool_d1 / pool_d2: sorted unique item ids, the sets test()'s negatives are drawn

@@ -1,0 +1,108 @@
+"""Time ONE evaluation batch of a variant SASRec model (isItC / isInC / isDR) the way train_sr.test() runs it, with device events.
+
+    python profiles/tools/eval_variant_time.py [--variant itc+dr] [--windows 5] [--bs 256] [--seq_len 20] [--emb 128] [--hid 32] [--neg 999]
+
+The default is run.sh's shape (train_sr_dr.py --model sasrec --isItC True --neg_nums 999: mybank, T 20, B 256, D 128, hid 32).  The tool
+calls SASRec.eval_ranks on an evaluation set resident in HBM and, where that returns None (a tree whose engine does not cover the model),
+the loop test() falls back to: model.forward + the masked BCE + the rank kernel per batch.  The package comes from PYTHONPATH when it is
+importable from there, so the same file measures two trees: PYTHONPATH=<other checkout> python profiles/tools/eval_variant_time.py.
+A window repeats the whole set until it lasts at least --min_s seconds between two events; one JSON line per run: the windows' ms per
+batch, their median and spread (max - min).  Per-launch times: rocprofv3 --kernel-trace --stats -- python ... --windows 1 --min_s 0.05.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+try:
+    import amid_amd  # noqa: F401
+except ImportError:
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+    import amid_amd  # noqa: F401
+
+from amid_amd import model_seq  # noqa: E402
+from amid_amd.utils import device_positive_ranks  # noqa: E402
+
+FIX = 1e-7
+
+
+def forward_loop(model, ep):
+    """train_sr.test()'s per-batch path (train_sr.py:55-64, :114-115)."""
+    bce = torch.nn.functional.binary_cross_entropy
+    out = []
+    for i in range(ep["seq_d1"].shape[0]):
+        outs = model(ep["user_node"][i], ep["i_node"][i], ep["neg_samples"][i], ep["seq_d1"][i], ep["seq_d2"][i], None, None, False)
+        B = ep["i_node"].shape[1]
+        p1, p2 = outs[0].reshape(B, -1), outs[1].reshape(B, -1)
+        m2 = ep["domain_id"][i].float().unsqueeze(1)
+        loss = (bce(p1, ep["label"], reduction="none") * (1 - m2) + bce(p2, ep["label"], reduction="none") * m2).mean()
+        out.append((loss, device_positive_ranks(p1, p2, ep["domain_id"][i], FIX)))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--variant", default="itc+dr", help="any of dr, itc, inc joined by +, or plain")
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--min_s", type=float, default=0.6)
+    ap.add_argument("--batches", type=int, default=16)
+    ap.add_argument("--bs", type=int, default=256)
+    ap.add_argument("--seq_len", type=int, default=20)
+    ap.add_argument("--emb", type=int, default=128)
+    ap.add_argument("--hid", type=int, default=32)
+    ap.add_argument("--neg", type=int, default=999)
+    ap.add_argument("--items", type=int, default=42441)
+    ap.add_argument("--tag", default="")
+    ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="A/B only: a class attribute of the engine, e.g. EVAL_FUSED=0")
+    args = ap.parse_args()
+    from amid_amd.engine import SasrecEngine
+    for kv in args.set:
+        name, _, val = kv.partition("=")
+        if not hasattr(SasrecEngine, name):
+            raise SystemExit(f"--set {kv}: SasrecEngine has no switch {name}")
+        cur = getattr(SasrecEngine, name)
+        setattr(SasrecEngine, name, (val not in ("0", "False", "false")) if isinstance(cur, bool) else type(cur)(val))
+    kinds = set(args.variant.split("+")) - {"plain"}
+    B, T, NI, nb, n = args.bs, args.seq_len, 1 + args.neg, args.batches, args.items
+    dev = torch.device("cuda:0")
+    model = model_seq.SASRec(10, args.emb, n + 1, args.emb, T, args.hid, B, "inc" in kinds, "itc" in kinds, 1.0 / B, 1.0 / B, isDR="dr" in kinds, seed=1)
+    model.eval()
+    g = torch.Generator().manual_seed(0)
+    seq = lambda: torch.where(torch.rand(nb, B, T, generator=g) < 0.7, torch.full((nb, B, T), n), torch.randint(1, n, (nb, B, T), generator=g))  # noqa: E731
+    label = torch.zeros(B, NI)
+    label[:, 0] = 1.0
+    ep = {"user_node": torch.zeros(nb, B, dtype=torch.int64), "i_node": torch.randint(1, n, (nb, B), generator=g),
+          "neg_samples": torch.randint(1, n, (nb, B, NI - 1), generator=g), "seq_d1": seq(), "seq_d2": seq(), "label": label,
+          "domain_id": torch.randint(0, 2, (nb, B), generator=g)}
+    ep = {k: v.to(dev) for k, v in ep.items()}
+    torch.cuda.synchronize()
+
+    with torch.no_grad():
+        path = "eval_ranks" if model.eval_ranks(ep, FIX) is not None else "forward"
+        run = (lambda: model.eval_ranks(ep, FIX)) if path == "eval_ranks" else (lambda: forward_loop(model, ep))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+        def window(reps):
+            e0.record()
+            for _ in range(reps):
+                run()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1)
+
+        for _ in range(3):
+            window(2)                                     # warm-up: graphs captured, code objects loaded, clocks up
+        reps = max(1, int(args.min_s * 1e3 / (window(4) / 4)) + 1)
+        ms = [window(reps) / (reps * nb) for _ in range(args.windows)]
+    print(json.dumps({"tag": args.tag, "set": args.set, "package": os.path.dirname(os.path.abspath(amid_amd.__file__)), "variant": args.variant, "path": path,
+                      "shape": {"B": B, "T": T, "D": args.emb, "hid": args.hid, "NI": NI}, "batches_per_window": reps * nb,
+                      "window_s": [round(m * reps * nb / 1e3, 3) for m in ms], "ms_per_batch": [round(m, 5) for m in ms],
+                      "median": round(statistics.median(ms), 5), "spread": round(max(ms) - min(ms), 5),
+                      "device": torch.cuda.get_device_name(0)}))
+
+
+if __name__ == "__main__":
+    main()
