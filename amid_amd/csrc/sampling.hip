@@ -49,7 +49,10 @@ __global__ __launch_bounds__(256) void sample_negatives_kernel(const NegArgs a) 
         if (ok && slot < a.k) { acc[slot] = cand; a.out[(long long)r * a.k + slot] = cand; }
         have = min(a.k, have + __popcll(m));
     }
-    if (have < a.k && lane == 0) a.out[(long long)r * a.k] = -1;                     // pool exhausted: reported by the host wrapper
+    // pool exhausted after 4096 rounds: slot 0 says so and nobody downstream looks for it.  DeviceBatches never sees it because its
+    // constructor refuses any row with k + |own| > |pool| (k <= 2048 eligible ids are all met long before 4096 x 64 draws); a direct
+    // caller of the C entry point checks out[r][0] itself
+    if (have < a.k && lane == 0) a.out[(long long)r * a.k] = -1;
 }
 
 }  // namespace amid

@@ -367,7 +367,11 @@ int amid_transpose_rect_f32(const float* const* src, float* const* dst, const in
 /* ---- data pipeline on the device (next-3 of SURVEY.md 8(f)) ------------------------------------------------------------------
  * replaces: random.sample(item_pool_d - set(own sequence), k) per sample in DualDomainSeqDataset.__getitem__ (dataset_seq.py:188,
  * :198, :206, :215): k distinct negatives per row, uniform over the row's domain pool minus its own items.  pool_d*: sorted unique
- * ids; own_items / own_off [N + 1]: the rows' own item ids, concatenated; out [N, k] (out[r][0] = -1: pool exhausted for row r). */
+ * ids; own_items / own_off [N + 1]: the rows' own item ids, concatenated; out [N, k].  k <= 2048 (4 rows x k ids in 64 KiB of LDS;
+ * above: AMID_ERR_UNSUPPORTED).  A row whose pool runs out (fewer than k eligible ids) gets out[r][0] = -1, the ids it found stay
+ * behind it and its other slots are not written.  Nothing here reports that mark: the caller either rules it out beforehand
+ * (DeviceBatches refuses a dataset with k + |own| > |pool| for any row) or reads out[r][0].  The draw is a pure function of
+ * (seed, epoch, r, pool, own, k), restated on the host by oracle/amid_oracle.py: sample_negatives_ref. */
 int amid_sample_negatives_i64(const long long* pool_d1, int n_pool_d1, const long long* pool_d2, int n_pool_d2,
                               const long long* own_items, const int* own_off, const long long* domain_id, int N, int k,
                               unsigned long long seed, unsigned epoch, long long* out, void* stream);

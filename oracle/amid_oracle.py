@@ -124,6 +124,7 @@ SITE_FFN2 = 3
 SITE_SUB_IN = 4     # BERT4Rec input_sublayer dropout
 SITE_SUB_OUT = 5    # BERT4Rec output_sublayer dropout
 SITE_BLOCK = 6      # BERT4Rec TransformerBlock.dropout
+SITE_NEG = 0x4E45   # the negative sampler (amid_amd/csrc/sampling.hip); outside the site_id() range of the dropout sites
 
 
 def site_id(domain: int, layer: int, kind: int) -> int:
@@ -173,6 +174,56 @@ def philox_masks_bert4rec(B: int, T: int, seed: int, step: int, p: float = BERT_
                 philox_keep_flat(B * T * D, seed, site_id(d, l, SITE_SUB_OUT), step, p).reshape(B, T, D))
             out[f"{pre}.{l}.block"] = torch.from_numpy(
                 philox_keep_flat(B * T * D, seed, site_id(d, l, SITE_BLOCK), step, p).reshape(B, T, D))
+    return out
+
+
+def _neg_candidates(pool: np.ndarray, r: int, round0: int, n_rounds: int, seed: int, epoch: int) -> np.ndarray:
+    """The candidates row r sees in rounds [round0, round0 + n_rounds), in (round, lane) order: 64 per round, the one of
+    (round, lane) is pool[(x * n) >> 32] with x the first word of Philox call (r << 20) | (round << 6) | lane at site
+    SITE_NEG, step word = epoch."""
+    idx = (np.uint64(r) << np.uint64(20)) | np.arange(round0 * 64, (round0 + n_rounds) * 64, dtype=np.uint64)
+    ctr = np.stack([
+        (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32),
+        (idx >> np.uint64(32)).astype(np.uint32),
+        np.full(idx.size, SITE_NEG, dtype=np.uint32),
+        np.full(idx.size, epoch & 0xFFFFFFFF, dtype=np.uint32),
+    ], axis=1)
+    x = philox4x32(ctr, (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))[:, 0].astype(np.uint64)
+    return pool[((x * np.uint64(len(pool))) >> np.uint64(32)).astype(np.int64)]
+
+
+def sample_negatives_ref(pool_d1, pool_d2, own_items, own_off, domain_id, k: int, seed: int, epoch: int,
+                         max_rounds: int = 4096) -> np.ndarray:
+    """Host restatement of amid_sample_negatives_i64 (amid_amd/csrc/sampling.hip; stands in for the reference's
+    random.sample(item_pool_d - set(own sequence), k), dataset_seq.py:188 / :198) -> int64 [N, k], integer for integer what the
+    kernel writes.  Row r reads a stream of candidates drawn uniformly from its domain's pool (domain_id[r] != 0 selects pool_d2),
+    64 per round (_neg_candidates), and keeps, in stream order, the first k that are neither in its own list
+    own_items[own_off[r]:own_off[r + 1]] nor kept already.  A row still short after max_rounds rounds gets -1 in slot 0; what it
+    kept stays in the slots behind it and the slots never reached stay 0 (the kernel leaves those untouched)."""
+    pools = (np.asarray(pool_d1, dtype=np.int64), np.asarray(pool_d2, dtype=np.int64))
+    own_items, own_off = np.asarray(own_items, dtype=np.int64), np.asarray(own_off, dtype=np.int64)
+    domain_id = np.asarray(domain_id)
+    out = np.zeros((len(domain_id), k), dtype=np.int64)
+    for r in range(len(domain_id)):
+        pool = pools[int(domain_id[r] != 0)]
+        own = own_items[own_off[r]:own_off[r + 1]]
+        kept: list = []
+        seen = set()
+        done, chunk = 0, 1                      # rounds are drawn in growing chunks: most rows need one round, an exhausted one all
+        while len(kept) < k and done < max_rounds:
+            chunk = min(chunk, max_rounds - done)
+            c = _neg_candidates(pool, r, done, chunk, seed, epoch)
+            c = c[~np.isin(c, own)]
+            first = np.sort(np.unique(c, return_index=True)[1])          # first occurrence of every distinct value, stream order
+            for v in c[first].tolist():
+                if v not in seen and len(kept) < k:
+                    seen.add(v)
+                    kept.append(v)
+            done += chunk
+            chunk = min(2 * chunk, 256)
+        out[r, :len(kept)] = kept
+        if len(kept) < k:
+            out[r, 0] = -1
     return out
 
 
