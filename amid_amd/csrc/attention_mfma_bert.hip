@@ -6,38 +6,12 @@
 // every key tile visited, keys >= T excluded, masked keys at -1e9 (a row whose keys are ALL masked gets the reference's uniform
 // softmax) and no score gradient through masked keys (masked_fill).
 #include "attention_mfma.h"
+#include "attention_bert_parts.h"
 
 namespace amid {
 
-constexpr int BHD = 32;
 constexpr int BERT_KT_LD = 68;                                  // row stride of the backward's K^T image
 constexpr int BERT_BWD_LDS_PER_WAVE = ATTN_BWD_LDS_PER_WAVE + BHD * BERT_KT_LD * 4;
-
-__device__ __forceinline__ f32x4 frag2(const float4 (&a)[2], const float4 (&b)[2], f32x4 c) {
-    c = mfma_frag(a[0], b[0], c);
-    return mfma_frag(a[1], b[1], c);
-}
-
-// bit (kj * 4 + r) of the result: key n = kj * 16 + 4 gq + r is inside the sequence (valid) / also visible (ok)
-__device__ __forceinline__ void key_bits(const unsigned char* __restrict__ kk, int T, int gq, unsigned& valid, unsigned& ok) {
-    // (the sixteen mask bytes of the lane are requested back to back, clamped instead of branched around: behind a branch per key each
-    // byte load waited out its own round trip -- sixteen dependent L2 latencies at the head of every wave)
-    unsigned char kb[16];
-#pragma unroll
-    for (int kj = 0; kj < 4; ++kj)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) kb[kj * 4 + r] = kk != nullptr ? kk[min(kj * 16 + 4 * gq + r, T - 1)] : (unsigned char)1;
-    valid = 0; ok = 0;
-#pragma unroll
-    for (int kj = 0; kj < 4; ++kj)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int n = kj * 16 + 4 * gq + r;
-            const unsigned bit = n < T ? 1u << (kj * 4 + r) : 0u;
-            valid |= bit;
-            ok |= kb[kj * 4 + r] != 0 ? bit : 0u;
-        }
-}
 
 // a.live (amid_live_list_i32): the launch covers the B listed sequences only -- workgroup j < live[B]: (0, live[j]), else (1, live[j])
 __device__ __forceinline__ int bert_live_seq(const AttnArgs& a, int j) {
@@ -60,29 +34,12 @@ __global__ __launch_bounds__(512) void attn_fwd_bert_kernel(const AttnArgs a) {
     const float inv = 1.0f / a.scale;
     const unsigned char* kk = a.key_keep ? a.key_keep + (long long)b * T : nullptr;
     if (TPW * qhalf >= NT) return;                         // (T <= 32: the second wave of a head has no query tile)
+    const BertGlobalLd ld{a.q, a.k, a.v, rowbase, T, D};
     float4 kf[4][2];
     float vt[4][4][2];
-    {   // K as row fragments; V^T (lane (m, g): key 16 kj + 4 g + r, dim 16 c + m) from V's row fragments by a 16 x 16 transpose through the
-        // wave's LDS tile -- as loads the transposed fragments were 32 four-byte requests per lane, each touching four 64-byte segments
+    {
         extern __shared__ __attribute__((aligned(16))) float fsmem[];
-        float* tile = fsmem + wave_id() * ATTN_BWD_TILE_FLOATS;
-        float4 vf[4][2];
-#pragma unroll
-        for (int kj = 0; kj < 4; ++kj)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                kf[kj][c] = ld4_row(a.k, rowbase, kj * 16 + m, T, D, h * BHD + 16 * c + 4 * gq);
-                vf[kj][c] = ld4_row(a.v, rowbase, kj * 16 + m, T, D, h * BHD + 16 * c + 4 * gq);
-            }
-#pragma unroll
-        for (int kj = 0; kj < 4; ++kj)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                float t4[4];
-                tile_transpose(tile, vf[kj][c], t4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) vt[kj][r][c] = t4[r];
-            }
+        bert_kv_frags(ld, h, fsmem + wave_id() * ATTN_BWD_TILE_FLOATS, kf, vt);
     }
     unsigned valid, okb;
     key_bits(kk, T, gq, valid, okb);
@@ -107,57 +64,22 @@ __global__ __launch_bounds__(512) void attn_fwd_bert_kernel(const AttnArgs a) {
 #pragma unroll
     for (int qq = 0; qq < TPW; ++qq)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) qall[qq][c] = ld4_row(a.q, rowbase, (TPW * qhalf + qq) * 16 + m, T, D, h * BHD + 16 * c + 4 * gq);
+        for (int c = 0; c < 2; ++c) qall[qq][c] = ld.q((TPW * qhalf + qq) * 16 + m, h * BHD + 16 * c + 4 * gq);
 #pragma unroll
     for (int qq = 0; qq < TPW; ++qq) {
         const int qi = TPW * qhalf + qq;
         if (qi >= NT) break;
         const int q = qi * 16 + m;
-        float4 qf[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) qf[c] = f4scale(qall[qq][c], inv);
         unsigned long long kw;
         if constexpr (WPH == 2) kw = shfl64(kw_own, qq * 16 + m) | shfl64(kw_own, 32 + qq * 16 + m);      // (both hold the whole word at other rates)
         else kw = shfl64(kw_own, qi * 16 + m);
-        f32x4 s[4];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kj = 0; kj < 4; ++kj) {
-            s[kj] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (kj < NT) {
-                s[kj] = frag2(kf[kj], qf, s[kj]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const unsigned bit = 1u << (kj * 4 + r);
-                    s[kj][r] = !(valid & bit) ? -INFINITY : ((okb & bit) ? s[kj][r] : -1e9f);
-                    mx = fmaxf(mx, s[kj][r]);
-                }
-            }
-        }
-        mx = quad_group_max(mx);
-        float l = 0.f;
-        f32x4 oacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int kj = 0; kj < 4; ++kj) {
-            if (kj < NT) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int n = kj * 16 + 4 * gq + r;
-                    const float p = fast_exp(s[kj][r] - mx);
-                    l += p;
-                    const float pd = ((kw >> n) & 1ull) ? p * a.dscale : 0.f;
-                    oacc[0] = mfma4(vt[kj][r][0], pd, oacc[0]);
-                    oacc[1] = mfma4(vt[kj][r][1], pd, oacc[1]);
-                }
-            }
-        }
-        l = quad_group_sum(l);
-        const float rl = 1.0f / l;
+        float4 ov[2];
+        float mx, rl;
+        bert_attn_qtile(kf, vt, qall[qq], inv, NT, valid, okb, kw, a.dscale, ov, mx, rl);
         if (q < T) {
 #pragma unroll
             for (int c = 0; c < 2; ++c)
-                st4(a.o + (rowbase + q) * D + h * BHD + 16 * c + 4 * gq,
-                    make_float4(oacc[c][0] * rl, oacc[c][1] * rl, oacc[c][2] * rl, oacc[c][3] * rl));
+                st4(a.o + (rowbase + q) * D + h * BHD + 16 * c + 4 * gq, ov[c]);
             if (gq == 0 && a.stats) {
                 float* sp = a.stats + ((rowbase + q) * H + h) * 2;
                 sp[0] = mx; sp[1] = rl;

@@ -80,6 +80,11 @@ template <int D> struct RingP3 {
         if (hi_late) dma.all(hslot(s - 1), cur);
         if (have_next) dma.all(hslot(s), nxt);
     }
+    // a chain that ENDED (its last product fetched nothing: mid and lo slots idle behind that product's barrier, the other hi slot idle
+    // too) starts again with weight W: the hi plane at once, the mid / lo planes when the caller is done with whatever it kept in
+    // their slots meanwhile (csrc/bert_seq_infer.hip: the K / V images of the attention core); then next() as after first()
+    __device__ __forceinline__ void restart_hi(const float* __restrict__ W) { cur = W; cur_hi_ready = true; dma.all(hslot(s), W); }
+    __device__ __forceinline__ void restart_ml() { dma.all(mslot(), cur + SLAB); dma.all(lslot(), cur + 2 * SLAB); }
     __device__ __forceinline__ void mid_sync() {
         if (hi_late) w_ring_wait();
         __syncthreads();

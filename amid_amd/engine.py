@@ -1455,7 +1455,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         self._eval_out(pl)
         L.call("amid_pack_indices_live", pl.in_i_node.data_ptr(), pl.in_neg.data_ptr(), pl.in_seq_d1.data_ptr(), pl.in_seq_d2.data_ptr(),
                B, shp.T, NI - 1, self.n_rows, pl.idx_all.data_ptr(), pl.err.data_ptr(), None, pl.domain.data_ptr(), pl.live.data_ptr(), s)
-        if self.inc_bs:           # enqueue_forward's launches up to the last encoder layer, the sequences' rows only
+        if self._eval_through_forward():           # enqueue_forward's launches up to the last encoder layer, the sequences' rows only
             self.enqueue_forward(pl, train=False, with_loss=False, head=False, gather_items=False)
         else:
             self._enqueue_eval_encoders(pl, build_images)
@@ -1474,9 +1474,23 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
                    pl.labels.data_ptr() if with_loss else None, pl.domain.data_ptr(), B, NI, D, self.hid, float(fix_value), *outs[:-1],
                    *mixargs, s)
             return
-        L.call("amid_eval_head_f32", pl.x[2].data_ptr(), self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"),
-               self.table.data_ptr(), ids, *self._scorer_ptrs(), pl.labels.data_ptr() if with_loss else None, pl.domain.data_ptr(), B, T, NI, D,
-               self.hid, SASREC_LN_EPS, float(fix_value), *outs)
+        ln_w, ln_b, ln_eps = self._eval_last_ln()
+        L.call("amid_eval_head_f32", pl.x[2].data_ptr(), ln_w, ln_b, self.table.data_ptr(), ids, *self._scorer_ptrs(),
+               pl.labels.data_ptr() if with_loss else None, pl.domain.data_ptr(), B, T, NI, D, self.hid, ln_eps, float(fix_value), *outs)
+
+    def _eval_through_forward(self) -> bool:
+        """Whether the evaluation batch's encoders are enqueue_forward's own launches (isInC: the token group in front of them)."""
+        return bool(self.inc_bs)
+
+    def _eval_last_ln(self):
+        """(gain pointers, bias pointers, eps) of the LayerNorm amid_eval_head_f32 applies in front of the mean over time (null pointers: none)."""
+        return self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"), SASREC_LN_EPS
+
+    def _enqueue_eval_images(self, pl: SasrecPlan) -> None:
+        """The weight images the evaluation's forward reads, built once per evaluation (eval_epoch: the batches' launches only read them)."""
+        if self._fwd_on_pieces(pl, pl.shape.B, pl.shape.Tenc):
+            src, w16 = self._w16_images(3)
+            lib().call("amid_sas_weights_bf16_planes", src, 24, self.D, 0, 3, w16.data_ptr(), self.s)
 
     def _enqueue_eval_encoders(self, pl: SasrecPlan, build_images: bool) -> None:
         """The sequences' rows and the inference forward of an evaluation batch, up to pl.x[2]: over the live list, or (a null list) over both
@@ -1569,9 +1583,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             self.capture_eval(pl, fix_value, with_loss)
         L = lib()
         with torch.cuda.stream(self.stream):
-            if self._fwd_on_pieces(pl, pl.shape.B, pl.shape.Tenc):      # this evaluation's weight images, once (the batches' launches only read them)
-                src, w16 = self._w16_images(3)
-                L.call("amid_sas_weights_bf16_planes", src, 24, self.D, 0, 3, w16.data_ptr(), self.s)
+            self._enqueue_eval_images(pl)      # this evaluation's weight images, once (the batches' launches only read them)
             for i in range(packed.shape[0]):
                 pl.in_pack.copy_(packed[i], non_blocking=True)
                 if use_graph:

@@ -124,7 +124,10 @@ class Bert4recEngine(SasrecEngine):
     STRIP_KERNELS = True         # the block's GEMM chains on csrc/bert_strip.hip (BertPlan.strip); bert.hip's row-tile kernels beyond 2 GiB
     SORT_RIDERS = False          # (the riders' host launches are the SASRec strip backward's)
     FUSED_TAIL = False           # (the one-launch step head and the folded tail are the SASRec step's)
-    EVAL_FUSED = False           # (the four-launch evaluation batch is the SASRec model's: engine.enqueue_eval)
+    EVAL_FUSED = True            # test() batches as one graph replay (engine.enqueue_eval on this model's encoders: _enqueue_eval_encoders)
+    # ... with the encoder as ONE launch where csrc/bert_seq_infer.hip covers the model (False: the strips, staged).  Both forms give the
+    # forward's bits; measured 0.189 against 0.233 ms per batch of 256 x 1 000 at T 50 (profiles/bert_eval.md)
+    EVAL_ONE_LAUNCH = True
     STRIP_P3 = True              # the strips' products on bf16 pieces at fp32 accuracy (csrc/bert_strip.hip MODE 3; False: fp32 matrix instructions)
 
     def live_forward_ok(self, pl) -> bool:
@@ -151,7 +154,7 @@ class Bert4recEngine(SasrecEngine):
         return bert4rec_dense_names(self.hid, self.dr, self.comp, self.inc_bs)
 
     # BERT4Rec has no last LayerNorm: the user vectors are the plain means over time (model_seq.py:299-300)
-    def _enqueue_user_vectors(self, pl) -> None:
+    def _enqueue_user_vectors(self, pl, mix: bool = True) -> None:
         shp = pl.shape
         lib().call("amid_lnmean_fwd_f32", pl.x[2].data_ptr(), None, None, None, None, shp.B, shp.Tenc, self.D, 0.0, pl.u.data_ptr(), self.s)
 
@@ -166,6 +169,31 @@ class Bert4recEngine(SasrecEngine):
         self.wT_sq = torch.zeros(2, 2, 4, D * D, dtype=torch.float32, device=self.device)
         self.w1T = torch.zeros(2, 2, D * F, dtype=torch.float32, device=self.device)
         self.w2T = torch.zeros(2, 2, F * D, dtype=torch.float32, device=self.device)
+
+    def _enqueue_comp_front(self, pl: BertPlan, gather_items: bool = True) -> None:
+        """The launches in front of a comp model's encoders (model_seq.py:283-294): the tiled key mask, the rows' gather, the comp scores and
+        the token group -> pl.x[0] (2T tokens a row).  gather_items=False: the sequences' rows only."""
+        L, s, shp, D = lib(), self.s, pl.shape, self.D
+        B = shp.B
+        c = self.comp
+        L.call("amid_key_keep_tiled_u8", pl.in_seq_d2.data_ptr(), B, shp.T, 2, pl.key_keep.data_ptr(), s)
+        L.call("amid_gather_rows_f32", self.table.data_ptr(), self.n_rows, D, pl.idx_all.data_ptr(), 0, shp.n_idx if gather_items else 2 * shp.Mi,
+               pl.xg.data_ptr(), None, s)
+        L.call("amid_bert_comp_score_f32", pl.xg.data_ptr(), B, shp.T, D, self.comp_cross, pl.inc_s.data_ptr(), s)
+        wts = (self._pp(c + "_d{d}.trans_nn.weight"), self._pp(c + "_d{d}.trans_nn.bias"), self._pp(c + "_d{d}.trans_bs.weight"),
+               self._pp(c + "_d{d}.trans_bs.bias"))
+        out = (pl.inc_gate.data_ptr(), pl.inc_S.data_ptr(), pl.inc_Z.data_ptr(), pl.inc_sw.data_ptr(), pl.x[0].data_ptr(), s)
+        if getattr(pl, "inc_world", 1) > 1:
+            # data parallel (as SasrecEngine's isInC branch): the softmax over the batch and Linear(bs, 1) span the GLOBAL batch -- the
+            # ranks all-gather their scores, form their rows' gates and partial token sums, all-reduce the sums and finish Z alike
+            ex = self._inc_exchange(pl)
+            self._coll(lambda: [ex.all_gather_packed(pl.inc_s[g], pl.inc_s_g[g]) for g in (0, 1)])
+            shard = (B, shp.T, D, self.inc_bs, ex.rank * B)
+            L.call("amid_bert_comp_fwd_shard_f32", pl.xg.data_ptr(), pl.inc_s_g.data_ptr(), *wts, self.inc_threshold, self.comp_cross, *shard, 1, *out)
+            self._coll(lambda: ex.all_reduce_dense(pl.inc_S))
+            L.call("amid_bert_comp_fwd_shard_f32", pl.xg.data_ptr(), pl.inc_s_g.data_ptr(), *wts, self.inc_threshold, self.comp_cross, *shard, 2, *out)
+        else:
+            L.call("amid_bert_comp_fwd_f32", pl.xg.data_ptr(), pl.inc_s.data_ptr(), *wts, self.inc_threshold, self.comp_cross, B, shp.T, D, *out)
 
     def enqueue_forward(self, pl: BertPlan, train: bool, with_loss: bool, sum_loss: bool = True) -> None:
         L, s, shp, D = lib(), self.s, pl.shape, self.D
@@ -182,24 +210,7 @@ class Bert4recEngine(SasrecEngine):
             L.call("amid_live_list_i32", pl.domain.data_ptr(), B, pl.live.data_ptr(), s)
         # model_seq.py:288: ONE mask, from domain 2, for both encoders
         if self.comp:      # :286 / :294 the T-token mask tiled twice over the 2T keys; the comp module's token group behind each row
-            c = self.comp
-            L.call("amid_key_keep_tiled_u8", pl.in_seq_d2.data_ptr(), B, shp.T, 2, pl.key_keep.data_ptr(), s)
-            L.call("amid_gather_rows_f32", self.table.data_ptr(), self.n_rows, D, pl.idx_all.data_ptr(), 0, shp.n_idx, pl.xg.data_ptr(), None, s)
-            L.call("amid_bert_comp_score_f32", pl.xg.data_ptr(), B, shp.T, D, self.comp_cross, pl.inc_s.data_ptr(), s)
-            wts = (self._pp(c + "_d{d}.trans_nn.weight"), self._pp(c + "_d{d}.trans_nn.bias"), self._pp(c + "_d{d}.trans_bs.weight"),
-                   self._pp(c + "_d{d}.trans_bs.bias"))
-            out = (pl.inc_gate.data_ptr(), pl.inc_S.data_ptr(), pl.inc_Z.data_ptr(), pl.inc_sw.data_ptr(), pl.x[0].data_ptr(), s)
-            if getattr(pl, "inc_world", 1) > 1:
-                # data parallel (as SasrecEngine's isInC branch): the softmax over the batch and Linear(bs, 1) span the GLOBAL batch -- the
-                # ranks all-gather their scores, form their rows' gates and partial token sums, all-reduce the sums and finish Z alike
-                ex = self._inc_exchange(pl)
-                self._coll(lambda: [ex.all_gather_packed(pl.inc_s[g], pl.inc_s_g[g]) for g in (0, 1)])
-                shard = (B, shp.T, D, self.inc_bs, ex.rank * B)
-                L.call("amid_bert_comp_fwd_shard_f32", pl.xg.data_ptr(), pl.inc_s_g.data_ptr(), *wts, self.inc_threshold, self.comp_cross, *shard, 1, *out)
-                self._coll(lambda: ex.all_reduce_dense(pl.inc_S))
-                L.call("amid_bert_comp_fwd_shard_f32", pl.xg.data_ptr(), pl.inc_s_g.data_ptr(), *wts, self.inc_threshold, self.comp_cross, *shard, 2, *out)
-            else:
-                L.call("amid_bert_comp_fwd_f32", pl.xg.data_ptr(), pl.inc_s.data_ptr(), *wts, self.inc_threshold, self.comp_cross, B, shp.T, D, *out)
+            self._enqueue_comp_front(pl)
         else:
             if not pl.strip:      # (strip path: the key mask rides in the first strip launch, _enqueue_blocks_strip)
                 L.call("amid_key_keep_u8", pl.in_seq_d2.data_ptr(), B * T, pl.key_keep.data_ptr(), s)
@@ -325,10 +336,11 @@ class Bert4recEngine(SasrecEngine):
             self._ptr_cache[key] = c
         return c
 
-    def _enqueue_blocks_strip(self, pl: BertPlan, lf, st, tr) -> None:
+    def _enqueue_blocks_strip(self, pl: BertPlan, lf, st, tr, save: bool = True, build_images: bool = True) -> None:
         """Both blocks on the strip kernels (csrc/bert_strip.hip): q / k / v of block 0, then per block the attention core and ONE launch
         for the out-projection, the feed-forward and -- block 0 -- the next block's LayerNorm + q / k / v.  lf: the live list (a train
-        step over the own-domain sequences) or None."""
+        step over the own-domain sequences) or None.  save=False (an inference forward): what only a backward reads -- y, x1, y2, pre, h,
+        the softmax statistics -- is not stored; build_images=False: the tile images are current."""
         L, s, shp, D = lib(), self.s, pl.shape, self.D
         B, T = shp.B, shp.Tenc
         live_attn = lf is not None
@@ -338,7 +350,7 @@ class Bert4recEngine(SasrecEngine):
         p3 = self._p3(pl)
         pl.p3_fwd = p3
         if p3:                       # this step's weight tiles as three-plane images (forward tiles and, for the backward, their transposes)
-            if not getattr(pl, "tiles_written", False):      # (the gather K1 of this forward wrote them with extra workgroups)
+            if build_images and not getattr(pl, "tiles_written", False):      # (the gather K1 of this forward wrote them with extra workgroups)
                 self._enqueue_tile_images()
             pl.tiles_written = False
             i0, i1 = self._block_img_ptrs(0), self._block_img_ptrs(1)
@@ -346,22 +358,94 @@ class Bert4recEngine(SasrecEngine):
         trl = self._transpose_lists() if pl.need_grad and not p3 else None
         pl.transposed_in_forward = trl is not None or p3
         n_tr = len(trl[2]) if trl else 0
-        L.call("amid_bert_strip_qkv_fwd_pro" + sfx, pl.x[0].data_ptr(), p0["la1"], p0["lb1"], i0["w3"] if p3 else p0["w3"], p0["b3"], B, T, lf, pl.y[0].data_ptr(),
+        sv = (lambda t: t.data_ptr()) if save else (lambda t: None)
+        L.call("amid_bert_strip_qkv_fwd_pro" + sfx, pl.x[0].data_ptr(), p0["la1"], p0["lb1"], i0["w3"] if p3 else p0["w3"], p0["b3"], B, T, lf, sv(pl.y[0]),
                pl.q[0].data_ptr(), pl.k[0].data_ptr(), pl.v[0].data_ptr(), None if self.comp else pl.in_seq_d2.data_ptr(), B * T,
                pl.key_keep.data_ptr(), trl[0] if trl else None, trl[1] if trl else None, trl[2] if trl else None, trl[3] if trl else None, n_tr, s)
         for l, p in ((0, p0), (1, p1)):
             if live_attn:
                 L.call("amid_attn_bert_fwd_live_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.key_keep.data_ptr(), B, T, D,
-                       self.H, l, st, tr, BERT_P_DROP, pl.o[l].data_ptr(), pl.stats[l].data_ptr(), lf, s)
+                       self.H, l, st, tr, BERT_P_DROP, pl.o[l].data_ptr(), sv(pl.stats[l]), lf, s)
             else:
                 L.call("amid_attn_fwd_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.key_keep.data_ptr(), B, T, D, self.H,
                        0, l, st, tr, BERT_P_DROP, pl.o[l].data_ptr(), pl.stats[l].data_ptr(), s)
-            nxt = ((p1["la1"], p1["lb1"], i1["w3"] if p3 else p1["w3"], p1["b3"], pl.y[1].data_ptr(), pl.q[1].data_ptr(), pl.k[1].data_ptr(), pl.v[1].data_ptr())
+            nxt = ((p1["la1"], p1["lb1"], i1["w3"] if p3 else p1["w3"], p1["b3"], sv(pl.y[1]), pl.q[1].data_ptr(), pl.k[1].data_ptr(), pl.v[1].data_ptr())
                    if l == 0 else (None,) * 8)
             w = (i0, i1)[l] if p3 else p
             L.call("amid_bert_strip_oproj_ffn_fwd" + sfx, pl.o[l].data_ptr(), pl.x[l].data_ptr(), w["wo"], p["bo"], p["la2"], p["lb2"], w["w1"],
-                   p["b1"], w["w2"], p["b2"], B, T, lf, l, st, tr, BERT_P_DROP, pl.x1[l].data_ptr(), pl.y2[l].data_ptr(), pl.pre[l].data_ptr(),
-                   pl.h[l].data_ptr(), pl.x[l + 1].data_ptr(), *nxt, s)
+                   p["b1"], w["w2"], p["b2"], B, T, lf, l, st, tr, BERT_P_DROP, sv(pl.x1[l]), sv(pl.y2[l]), sv(pl.pre[l]),
+                   sv(pl.h[l]), pl.x[l + 1].data_ptr(), *nxt, s)
+
+    # ------------------------------------------------------------------ evaluation: test(), train_sr.py:31-128 (engine.enqueue_eval)
+    # The batch is amid_pack_indices_live (index marshal + live list), the encoders over the B own-domain sequences, amid_eval_head_f32 with null
+    # LayerNorm pointers (the plain mean over time, model_seq.py:299-300; the scorer over the gathered candidates, masked BCE, both ranks).
+    #   one launch (EVAL_ONE_LAUNCH; the plain and isDR models on bf16 pieces, T <= 64): amid_bert_seq_fwd_gather_infer_f32 -- the gather, both
+    #           blocks and their attention cores in one workgroup per sequence, only pl.x[2] written: three launches a batch.
+    #   staged: amid_embed_fwd_live_f32 (a comp model: its gather / score / token-group launches, the sequences' rows only), then the strip
+    #           launches of enqueue_forward over the live list with null saved-tensor pointers (y, x1, y2, pre, h, stats are not stored).
+    #   isDR:   + amid_lnmean_fwd_f32 and amid_eval_head_u_f32 on its vector (the launch the model's forward forms pl.u with, so the same
+    #           bits); predict_ips / predict_gfunc are not evaluated: test() reads outs[0], outs[1] only.
+    # Both forms give every live row of pl.x[2] the bits of enqueue_forward(train=False): the chains and the attention core are the same
+    # device functions (csrc/bert_strip_parts.h, attention_bert_parts.h) and every one of their operations is row-independent.
+    def eval_fused_ok(self, pl) -> bool:
+        shp = pl.shape
+        if not self.EVAL_FUSED or not getattr(pl, "strip", False) or self.input_pool(pl) is not None:
+            return False
+        if getattr(pl, "itc_world", 1) != 1 or getattr(pl, "inc_world", 1) != 1:      # a data-parallel shard of a comp batch keeps enqueue_forward
+            return False
+        if not lib().value("amid_attn_bert_live_supported", shp.Tenc, self.D, self.H):
+            return False
+        return bool(self.D % 32 == 0 and self.D <= 128 and 0 < self.hid <= 64 and self.hid % 4 == 0)      # the head's limits (amid_eval_head_f32)
+
+    def _eval_through_forward(self) -> bool:
+        return False
+
+    def _eval_last_ln(self):
+        return None, None, 0.0
+
+    def _enqueue_eval_images(self, pl) -> None:
+        if self._p3(pl):
+            self._enqueue_tile_images()
+
+    def _eval_one_launch(self, pl) -> bool:
+        shp = pl.shape
+        return bool(self.EVAL_ONE_LAUNCH and not self.comp and self._p3(pl)
+                    and lib().value("amid_bert_seq_infer_supported", shp.B, shp.Tenc, self.D, self.H))
+
+    def _seq_infer_ptrs(self):
+        """The one-launch encoder's pointer arrays: [block][domain] families (w3 / b3: [block][q, k, v][domain]), weights as tile images."""
+        c = self._ptr_cache.get("bert_seq_infer")
+        if c is None:
+            fp, I = self.dense, self._img
+            fam = lambda fmt: ptr_array([fp.ptr(fmt.format(d=d, l=l)) for l in (0, 1) for d in (1, 2)])      # noqa: E731
+            img = lambda i: ptr_array([I(l, g, i) for l in (0, 1) for g in (0, 1)])                          # noqa: E731
+            c = (fam("transform{d}.{l}.input_sublayer.norm.a_2"), fam("transform{d}.{l}.input_sublayer.norm.b_2"),
+                 ptr_array([I(l, g, j) for l in (0, 1) for j in range(3) for g in (0, 1)]),
+                 ptr_array([fp.ptr(f"transform{d}.{l}.attention.linear_layers.{j}.bias") for l in (0, 1) for j in range(3) for d in (1, 2)]),
+                 img(3), fam("transform{d}.{l}.attention.output_linear.bias"),
+                 fam("transform{d}.{l}.output_sublayer.norm.a_2"), fam("transform{d}.{l}.output_sublayer.norm.b_2"),
+                 img(4), fam("transform{d}.{l}.feed_forward.w_1.bias"), img(8), fam("transform{d}.{l}.feed_forward.w_2.bias"))
+            self._ptr_cache["bert_seq_infer"] = c
+        return c
+
+    def _enqueue_eval_encoders(self, pl, build_images: bool) -> None:
+        """The own-domain sequences' rows and the inference forward of an evaluation batch, up to pl.x[2] (the live rows only)."""
+        L, s, shp, D = lib(), self.s, pl.shape, self.D
+        B, T = shp.B, shp.Tenc
+        lf, st = pl.live.data_ptr(), self.step_state.data_ptr()
+        if build_images:
+            self._enqueue_eval_images(pl)
+        pl.tiles_written = False
+        if self._eval_one_launch(pl):
+            L.call("amid_bert_seq_fwd_gather_infer_f32", pl.x[2].data_ptr(), *self._seq_infer_ptrs(), B, T, lf, self.table.data_ptr(), self.n_rows,
+                   pl.idx_all.data_ptr(), pl.in_seq_d2.data_ptr(), s)
+            return
+        if self.comp:
+            self._enqueue_comp_front(pl, gather_items=False)
+        else:
+            L.call("amid_embed_fwd_live_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), None, None, B, T, D, 0, pl.xg.data_ptr(), None, st, 0,
+                   0.0, lf, s)
+        self._enqueue_blocks_strip(pl, lf, st, 0, save=False, build_images=False)
 
     def _enqueue_blocks_rowtile(self, pl: BertPlan, st, tr) -> None:
         L, s, shp, D = lib(), self.s, pl.shape, self.D

@@ -303,8 +303,10 @@ class SASRec(nn.Module):
         the positive's rank with and without fix_value (:114-115; utils.py:21-40, :296-297) -- three launches replayed as one graph
         (SasrecEngine.enqueue_eval; isDR / isItC / isInC models: the launches their forward forms the user vectors with, both domains'
         sequences where a comp module needs them, and the same scorer launch).  Returns device tensors rank [n, B], rank_raw [n, B]
-        (int32) and loss [n], or None when this model evaluates through forward() (BERT4Rec, shapes the engine's evaluation does not cover,
-        a comp model whose batch is not its bs rows: forward() then raises what it always raised)."""
+        (int32) and loss [n], or None when this model evaluates through forward() (shapes the engine's evaluation does not cover -- for
+        BERT4Rec: more than 64 encoder tokens, a row-tile plan --, a comp model whose batch is not its bs rows: forward() then raises what it
+        always raised).  BERT4Rec (plain, isDR, isInC, isItC) runs the same batch on its own encoders: one launch for both blocks, or the
+        strips staged (Bert4recEngine._enqueue_eval_encoders)."""
         eng = self.engine
         nb, B, T = ep["seq_d1"].shape
         neg = ep["neg_samples"].reshape(nb, B, -1)

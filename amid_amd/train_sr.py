@@ -217,10 +217,10 @@ def test(model, args, val_batches):
     model.eval()
     stats = AverageMeter("loss", "loss_cls")
     ranks, ranks_raw, doms, ovs, losses = [], [], [], [], []
-    # the SASRec models (plain, isDR, isItC, isInC and their combinations on one GPU): the whole evaluation set resident in HBM, per batch
+    # the SASRec and BERT4Rec models (plain, isDR, isItC, isInC and their combinations on one GPU): the whole evaluation set resident in HBM, per batch
     # one graph replay -- for the plain and isDR models the own domain's sequence only (the other domain's logits are never read:
     # utils.py:21-40, train_sr.py:63-64), both domains where a comp module couples them --, candidates gathered inside the scorer, BCE and
-    # both ranks in the same launch (SASRec.eval_ranks); BERT4Rec and shapes the engine does not cover go through model.forward below
+    # both ranks in the same launch (SASRec.eval_ranks / BERT4Rec's, inherited); shapes the engine does not cover go through model.forward below
     fused, ep, loader = None, None, val_batches
     if hasattr(model, "eval_ranks") and hasattr(val_batches, "epoch_tensors") and len(val_batches) > 0:
         ep = val_batches.epoch_tensors()

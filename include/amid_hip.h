@@ -1067,6 +1067,26 @@ int amid_topk_f32(const float* u, long long u_dom_stride, const long long* domai
  * w1T, w2T -- the FIRST of the matrix's four tiles' images, the others 3 * 128 * 128 bf16 further each (w_1 [512][128] and w_2^T: row blocks;
  * w_2 [128][512] and w_1^T: column blocks). */
 int amid_bert_weight_images_f32(const float* const* src, const int* ld, const int* tr, int n, void* dst16, void* stream);
+/* BERT4Rec's inference encoder as ONE launch (csrc/bert_seq_infer.hip; evaluation, engine_bert.py): a workgroup per sequence of the live list
+ * (amid_live_list_i32 / amid_pack_indices_live: slot j < live[B] -> (domain 0, live[j]), else (domain 1, live[j])) gathers the sequence's T rows
+ * table[idx_all[g][b][t]] (idx_all = the batch's index list [seq_d1 B T | seq_d2 B T | ...], ids clamped to n_rows), forms the key mask of both
+ * encoders from row b of seq_d2 (> 0, model_seq.py:288), runs both TransformerBlocks in eval mode and writes ONLY its T rows of x_out
+ * [2, B, T, 128] -- the bits amid_embed_fwd_live_f32 + the *_p3_f32 strip launches + amid_attn_bert_fwd_live_f32 give those rows (the chains and
+ * the attention core are the same device functions).  No saved tensor, no dropout draw, no key-mask bytes.
+ * Host arrays of device pointers: la1, lb1 (LNb_in), wo_img, bo, la2, lb2 (LNb_out), w1_img, b1, w2_img, b2 -- 4 entries ordered
+ * [block][domain]; w3_img, b3 -- 12 entries ordered [block][q, k, v][domain].  Every *_img is a three-plane tile image of
+ * amid_bert_weight_images_f32 (w1_img / w2_img: the first of the four tiles' images), which must be current; the kernel only reads them.
+ * amid_bert_seq_infer_supported: 1 for D == 128, H == 4, 0 < T <= 64, B > 0.  Null pointers, B <= 0, T <= 0, n_rows <= 0: AMID_ERR_ARG; any
+ * other shape outside the supported ones: AMID_ERR_UNSUPPORTED -- both before anything touches a device.
+ * The strip entry points amid_bert_strip_qkv_fwd_pro*_f32 / amid_bert_strip_oproj_ffn_fwd*_f32 accept NULL for y / x1, y2, pre, h, ny: "do not
+ * store" (the staged inference forward); a non-null pointer behaves as before. */
+int amid_bert_seq_infer_supported(int B, int T, int D, int H);
+int amid_bert_seq_fwd_gather_infer_f32(float* x_out, const float* const* la1, const float* const* lb1, const float* const* w3_img,
+                                       const float* const* b3, const float* const* wo_img, const float* const* bo,
+                                       const float* const* la2, const float* const* lb2, const float* const* w1_img,
+                                       const float* const* b1, const float* const* w2_img, const float* const* b2, int B, int T,
+                                       const int* live, const float* table, long long n_rows, const int* idx_all,
+                                       const long long* seq_d2, void* stream);
 /* BERT4Rec(isInC / isItC) under data parallel (round 5): amid_bert_comp_fwd_f32 / _bwd_f32 (model_seq.py:283-294 and its autograd) on a
  * shard of the global batch, cut at the all-reduces of the token sums S (forward) and of their gradient dZ (backward) exactly as
  * amid_inc_embed_fwd_shard_f32 / amid_inc_bwd_shard_f32: B rows = samples j0 .. j0 + B - 1 of Bg, s_all [2, Bg] the all-gathered scores. */

@@ -1,6 +1,7 @@
-"""Time ONE evaluation batch of a variant SASRec model (isItC / isInC / isDR) the way train_sr.test() runs it, with device events.
+"""Time ONE evaluation batch of a SASRec or BERT4Rec model (plain or isItC / isInC / isDR) the way train_sr.test() runs it, with device events.
 
-    python profiles/tools/eval_variant_time.py [--variant itc+dr] [--windows 5] [--bs 256] [--seq_len 20] [--emb 128] [--hid 32] [--neg 999]
+    python profiles/tools/eval_variant_time.py [--model sasrec|bert4rec] [--variant itc+dr] [--windows 5] [--bs 256] [--seq_len 20] [--emb 128]
+                                               [--hid 32] [--neg 999] [--set EVAL_ONE_LAUNCH=0]
 
 The default is run.sh's shape (train_sr_dr.py --model sasrec --isItC True --neg_nums 999: mybank, T 20, B 256, D 128, hid 32).  The tool
 calls SASRec.eval_ranks on an evaluation set resident in HBM and, where that returns None (a tree whose engine does not cover the model),
@@ -45,6 +46,7 @@ def forward_loop(model, ep):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="sasrec", choices=("sasrec", "bert4rec"), help="bert4rec: emb is 128 whatever --emb says (the reference hard-codes it)")
     ap.add_argument("--variant", default="itc+dr", help="any of dr, itc, inc joined by +, or plain")
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--min_s", type=float, default=0.6)
@@ -58,17 +60,21 @@ def main():
     ap.add_argument("--tag", default="")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="A/B only: a class attribute of the engine, e.g. EVAL_FUSED=0")
     args = ap.parse_args()
-    from amid_amd.engine import SasrecEngine
+    bert = args.model == "bert4rec"
+    if bert:
+        args.emb = 128
+    cls = model_seq.BERT4Rec if bert else model_seq.SASRec
+    eng_cls = cls.ENGINE_CLS
     for kv in args.set:
         name, _, val = kv.partition("=")
-        if not hasattr(SasrecEngine, name):
-            raise SystemExit(f"--set {kv}: SasrecEngine has no switch {name}")
-        cur = getattr(SasrecEngine, name)
-        setattr(SasrecEngine, name, (val not in ("0", "False", "false")) if isinstance(cur, bool) else type(cur)(val))
+        if not hasattr(eng_cls, name):
+            raise SystemExit(f"--set {kv}: {eng_cls.__name__} has no switch {name}")
+        cur = getattr(eng_cls, name)
+        setattr(eng_cls, name, (val not in ("0", "False", "false")) if isinstance(cur, bool) else type(cur)(val))
     kinds = set(args.variant.split("+")) - {"plain"}
     B, T, NI, nb, n = args.bs, args.seq_len, 1 + args.neg, args.batches, args.items
     dev = torch.device("cuda:0")
-    model = model_seq.SASRec(10, args.emb, n + 1, args.emb, T, args.hid, B, "inc" in kinds, "itc" in kinds, 1.0 / B, 1.0 / B, isDR="dr" in kinds, seed=1)
+    model = cls(10, args.emb, n + 1, args.emb, T, args.hid, B, "inc" in kinds, "itc" in kinds, 1.0 / B, 1.0 / B, isDR="dr" in kinds, seed=1)
     model.eval()
     g = torch.Generator().manual_seed(0)
     seq = lambda: torch.where(torch.rand(nb, B, T, generator=g) < 0.7, torch.full((nb, B, T), n), torch.randint(1, n, (nb, B, T), generator=g))  # noqa: E731
@@ -97,7 +103,7 @@ def main():
             window(2)                                     # warm-up: graphs captured, code objects loaded, clocks up
         reps = max(1, int(args.min_s * 1e3 / (window(4) / 4)) + 1)
         ms = [window(reps) / (reps * nb) for _ in range(args.windows)]
-    print(json.dumps({"tag": args.tag, "set": args.set, "package": os.path.dirname(os.path.abspath(amid_amd.__file__)), "variant": args.variant, "path": path,
+    print(json.dumps({"tag": args.tag, "set": args.set, "package": os.path.dirname(os.path.abspath(amid_amd.__file__)), "model": args.model, "variant": args.variant, "path": path,
                       "shape": {"B": B, "T": T, "D": args.emb, "hid": args.hid, "NI": NI}, "batches_per_window": reps * nb,
                       "window_s": [round(m * reps * nb / 1e3, 3) for m in ms], "ms_per_batch": [round(m, 5) for m in ms],
                       "median": round(statistics.median(ms), 5), "spread": round(max(ms) - min(ms), 5),
