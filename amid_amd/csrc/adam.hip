@@ -880,6 +880,8 @@ extern "C" int amid_optimizer_step_gathered_f32(float* p, float* m, float* v, fl
     AMID_CHECK_ARG(world > 0 && world <= 16 && umax > 0 && id_rows * (long long)D >= umax && (chunk_floats % 4) == 0 &&
                    (dense_off < 0 ? chunk_floats >= (long long)(id_rows + umax) * D
                                   : (dense_off >= (long long)(id_rows + umax) * D && (dense_off % 4) == 0 && chunk_floats >= dense_off + n)));
+    // lane r of a half-wave hands rank r's search result to the column loop, where only the first D / 4 lanes are alive
+    if (D < 4 * world) return AMID_ERR_UNSUPPORTED;
     long long db = (n / 4 + 255) / 256;
     if (db < 1) db = 1;
     if (db > 1024) db = 1024;

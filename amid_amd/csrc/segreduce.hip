@@ -131,10 +131,12 @@ __global__ __launch_bounds__(1024) void segreduce_spans_pack_kernel(const int* _
 // Data-parallel exchange: a rank's (unique ids, gradient rows) padded to the world's largest count with (pad_id, zero row)
 // pairs (amid_amd/dist.py); pad_id < 0 = repeat the first id (adds exact zeros to a real row).  One half-wave per row.
 // Blocks past n_pad (optional) run fixed-order sums of reduce_partials.h: the copy of the flat dense gradient behind the rows.
+// A list longer than n_out does not fit: the rows past n_out are dropped and err (optional) gets AMID_FLAG_UMAX_EXCEEDED -- the eager
+// step's counterpart of the packing tails' flag (segreduce_spans_pack_kernel above).
 __global__ __launch_bounds__(256) void sparse_pad_kernel(const int* __restrict__ ids, const float* __restrict__ rows,
                                                          const int* __restrict__ n_uniq, int n_out, int D, int pad_id,
                                                          int* __restrict__ out_ids, float* __restrict__ out_rows, int n_pad,
-                                                         const ReduceEntry* __restrict__ entries, int red_bx) {
+                                                         const ReduceEntry* __restrict__ entries, int red_bx, int* __restrict__ err) {
     if ((int)blockIdx.x >= n_pad) {
         const int rb = blockIdx.x - n_pad;
         reduce_partials_block(entries[rb / red_bx], rb % red_bx, red_bx);
@@ -145,6 +147,7 @@ __global__ __launch_bounds__(256) void sparse_pad_kernel(const int* __restrict__
     if (r >= n_out) return;
     const int n = *n_uniq;
     const bool live = r < n;
+    if (r == 0 && sub == 0 && err != nullptr && n > n_out) atomicOr(err, AMID_FLAG_UMAX_EXCEEDED);
     if (sub == 0) out_ids[r] = live ? ids[r] : (pad_id < 0 ? ids[0] : pad_id);
     for (int c = sub; c < (D >> 2); c += 32)
         st4(out_rows + (long long)r * D + 4 * c, live ? ld4(rows + (long long)r * D + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f));
@@ -326,27 +329,27 @@ extern "C" int amid_grad_tail_pack_f32(const float* grad_rows, const int* pos_so
 }
 
 static int sparse_pad(const int* uniq_ids, const float* uniq_rows, const int* n_uniq, int n_out, int D, int pad_id, int* out_ids,
-                      float* out_rows, const void* entries_dev, int n_entries, int max_count, void* stream) {
+                      float* out_rows, const void* entries_dev, int n_entries, int max_count, int* err_flag, void* stream) {
     AMID_CHECK_ARG(uniq_ids && uniq_rows && n_uniq && out_ids && out_rows && n_out > 0 && D > 0 && (D % 4) == 0);
     AMID_CHECK_ARG(n_entries == 0 || (entries_dev && n_entries > 0 && max_count > 0));
     const int n_pad = (n_out + 7) / 8;
     int bx = n_entries ? (max_count + 127) / 128 : 0;
     if (bx > 512) bx = 512;
     sparse_pad_kernel<<<n_pad + bx * n_entries, 256, 0, (hipStream_t)stream>>>(uniq_ids, uniq_rows, n_uniq, n_out, D, pad_id, out_ids, out_rows,
-                                                                              n_pad, (const ReduceEntry*)entries_dev, bx > 0 ? bx : 1);
+                                                                              n_pad, (const ReduceEntry*)entries_dev, bx > 0 ? bx : 1, err_flag);
     AMID_LAUNCH_CHECK();
     return AMID_OK;
 }
 
 extern "C" int amid_sparse_pad_f32(const int* uniq_ids, const float* uniq_rows, const int* n_uniq, int n_out, int D, int pad_id,
-                                   int* out_ids, float* out_rows, void* stream) {
-    return sparse_pad(uniq_ids, uniq_rows, n_uniq, n_out, D, pad_id, out_ids, out_rows, nullptr, 0, 0, stream);
+                                   int* out_ids, float* out_rows, int* err_flag, void* stream) {
+    return sparse_pad(uniq_ids, uniq_rows, n_uniq, n_out, D, pad_id, out_ids, out_rows, nullptr, 0, 0, err_flag, stream);
 }
 
 // the same padding with `n_entries` fixed-order sums (amid_reduce_entry_pack tables) in the same launch
 extern "C" int amid_sparse_pad_sum_f32(const int* uniq_ids, const float* uniq_rows, const int* n_uniq, int n_out, int D, int pad_id,
                                        int* out_ids, float* out_rows, const void* entries_dev, int n_entries, int max_count,
-                                       void* stream) {
+                                       int* err_flag, void* stream) {
     AMID_CHECK_ARG(entries_dev && n_entries > 0);
-    return sparse_pad(uniq_ids, uniq_rows, n_uniq, n_out, D, pad_id, out_ids, out_rows, entries_dev, n_entries, max_count, stream);
+    return sparse_pad(uniq_ids, uniq_rows, n_uniq, n_out, D, pad_id, out_ids, out_rows, entries_dev, n_entries, max_count, err_flag, stream);
 }

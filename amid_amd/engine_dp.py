@@ -108,7 +108,16 @@ class DataParallelMixin:
             else:
                 self.enqueue_local_grads(pl)
             exchange.all_reduce_dense(self.dense.grad)
-            merged = exchange.exchange_sparse(pl.uniq_ids, pl.uniq_grad, pl.n_uniq, umax=umax)
+            # the eager exchange pads this rank's list to umax entries: a list that does not fit raises the flag in the plan's error word from
+            # the padding launch itself (no launch of its own, no host synchronisation), as the packing tails of graph A do
+            be = getattr(exchange, "backend", None)
+            if hasattr(be, "err"):
+                be.err = pl.err
+            try:
+                merged = exchange.exchange_sparse(pl.uniq_ids, pl.uniq_grad, pl.n_uniq, umax=umax)
+            finally:
+                if hasattr(be, "err"):
+                    be.err = None
             self.enqueue_optimizer(pl, sparse=merged if exchange.active else None)
         if fast:                               # this step ran eagerly (it also warmed every kernel up); capture the pair for the next ones
             with torch.cuda.stream(self.stream):      # (the comp models' steps hold torch copies: they must land on the capturing stream)
@@ -204,6 +213,7 @@ class HipMergeBackend:
         self.all = torch.zeros((self.cap + (self.cap + D - 1) // D + 16 * 16 + self.MAX_WORLD * self.dense_rows) * D, dtype=torch.float32,
                                device=dev)
         self._entries = {}
+        self.err: Optional[torch.Tensor] = None      # the step's error word (train_step_dp sets it around the eager exchange): pad_packed's flag
         # owner-bucketed exchange (dist.SparseDenseExchange._exchange_owner): per-owner counts (+ the fill's overflow flag)
         self.owner_ws = torch.empty(L.value("amid_owner_workspace_bytes", self.cap), dtype=torch.uint8, device=dev)
         self.owner_counts = torch.zeros(self.MAX_WORLD + 1, dtype=torch.int32, device=dev)
@@ -275,14 +285,15 @@ class HipMergeBackend:
         D = self.eng.D
         id_rows, rows = packed_rows(umax, D)
         send = self.send[: self.chunk_rows(umax, dense) * D]
+        err = self.err.data_ptr() if self.err is not None else None      # a list of more than umax entries: AMID_FLAG_UMAX_EXCEEDED
         # sentinel padding (one past the last table row) keeps every rank's list sorted, so merge_packed() is a merge, not a sort
         if dense is not None:          # the copy of the flat dense gradient behind the rows rides in the padding launch
             ent = self._entry(("copy", umax), dense.data_ptr(), send.data_ptr() + 4 * rows * D, 0, 1, dense.numel())
             lib().call("amid_sparse_pad_sum_f32", uniq_ids.data_ptr(), uniq_rows.data_ptr(), n_uniq.data_ptr(), umax, D, self.eng.n_rows,
-                       send.data_ptr(), send.data_ptr() + 4 * id_rows * D, ent.data_ptr(), 1, dense.numel(), self.eng.s)
+                       send.data_ptr(), send.data_ptr() + 4 * id_rows * D, ent.data_ptr(), 1, dense.numel(), err, self.eng.s)
         else:
             lib().call("amid_sparse_pad_f32", uniq_ids.data_ptr(), uniq_rows.data_ptr(), n_uniq.data_ptr(), umax, D, self.eng.n_rows,
-                       send.data_ptr(), send.data_ptr() + 4 * id_rows * D, self.eng.s)
+                       send.data_ptr(), send.data_ptr() + 4 * id_rows * D, err, self.eng.s)
         return send
 
     def gather_buffer(self, world: int, umax: int, dense: Optional[torch.Tensor] = None) -> torch.Tensor:

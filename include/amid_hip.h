@@ -30,7 +30,9 @@ extern "C" {
 #define AMID_ERR_ARG (-1)
 #define AMID_ERR_UNSUPPORTED (-2)
 /* bits of a plan's device error word (err_flag arguments): 1 = an item index outside the table (nn.Embedding would raise,
- * model_seq.py:27-29); 2 = a data-parallel step found more unique rows than the caller's bound umax (amid_grad_tail_pack_f32) */
+ * model_seq.py:27-29); 2 = a data-parallel step found more unique rows than the caller's bound umax (the packing tails
+ * amid_grad_tail_pack_f32 / amid_grad_tail_live_dp_f32 / amid_grad_tail_live_dp1_f32 and the eager step's amid_sparse_pad_f32 /
+ * amid_sparse_pad_sum_f32) */
 #define AMID_FLAG_INDEX_RANGE (1)
 #define AMID_FLAG_UMAX_EXCEEDED (2)
 
@@ -107,21 +109,25 @@ int amid_embgrad_segreduce_f32(const float* grad_rows /* [n_idx, D] */, const in
 
 /* data-parallel exchange helpers (no reference counterpart: the reference is single-GPU, train_sr.py:473).
  * pad: a rank's segment-reduced (ids, rows) padded to n_out entries with (pad_id, zero row) pairs (pad_id < 0: repeat the first id);
- * n_uniq is a device scalar.
+ * n_uniq is a device scalar.  A list of more than n_out entries does not fit: the entries past n_out are dropped and err_flag (optional,
+ * device int) gets AMID_FLAG_UMAX_EXCEEDED, as in the packing tails; a list that fits leaves the word alone.
  * merge: `world` (<= 16) lists of `len` non-decreasing keys (ascending unique ids, then `sentinel` > every id as padding), rank r's
  * list at keys + r * key_stride, merged stably in rank order -> the outputs of amid_sort_unique_i32 on the concatenation, except that
  * pos_sorted holds row_base + r * row_stride + i for entry (r, i): the row of its gradient in the caller's gathered buffer (packed
  * exchange: ids and rows of a rank travel in one buffer); the sentinel run is left out of n_uniq.
  * workspace: amid_sort_unique_workspace_bytes(world * len). */
 int amid_sparse_pad_f32(const int* uniq_ids, const float* uniq_rows, const int* n_uniq, int n_out, int D, int pad_id, int* out_ids,
-                        float* out_rows, void* stream);
+                        float* out_rows, int* err_flag, void* stream);
 int amid_merge_sorted_lists_i32(const int* keys, int world, int len, long long key_stride, int row_base, int row_stride, int sentinel,
                                 void* workspace, int* pos_sorted, int* uniq_ids, int* seg_off, int* seg_of, int* n_uniq, void* stream);
 /* the two helpers with `n_entries` fixed-order sums (tables of amid_reduce_entry_pack, semantics of amid_reduce_partials_f32) riding in
  * their first launch: the data-parallel step copies its flat dense gradient behind the padded rows (pad) and sums the ranks' dense
- * parts in rank order (merge) without a launch of their own -- both are independent of the sparse work they ride with. */
+ * parts in rank order (merge) without a launch of their own -- both are independent of the sparse work they ride with.
+ * Rank order is a promise of the aligned path of the fixed-order sums only: count and stride multiples of 4, 16-byte aligned pointers, at
+ * most 32 partials -- what the data-parallel step always gives it (every slot of the flat buffer is padded to 4 floats, at most 16 ranks).
+ * Anything else takes the scalar path, which is still a fixed order, the same on every rank, but adds partials k and k + 8 first. */
 int amid_sparse_pad_sum_f32(const int* uniq_ids, const float* uniq_rows, const int* n_uniq, int n_out, int D, int pad_id, int* out_ids,
-                            float* out_rows, const void* entries_dev, int n_entries, int max_count, void* stream);
+                            float* out_rows, const void* entries_dev, int n_entries, int max_count, int* err_flag, void* stream);
 int amid_merge_sorted_lists_sum_i32(const int* keys, int world, int len, long long key_stride, int row_base, int row_stride, int sentinel,
                                     void* workspace, int* pos_sorted, int* uniq_ids, int* seg_off, int* seg_of, int* n_uniq,
                                     const void* entries_dev, int n_entries, int max_count, void* stream);
@@ -184,7 +190,10 @@ int amid_optimizer_step_f32(float* p, float* m, float* v, const float* g, long l
  * (> every id) | umax gradient rows | at dense_off: the rank's flat dense gradient, n floats].  g <- the ranks' dense parts summed in
  * rank order, then dense Adam; every table row whose id occurs in some chunk gets the lazy row Adam with the rows of equal ids
  * summed in rank order.  world <= 16; dense_off and chunk_floats multiples of 4.  dense_off < 0: the chunks carry no dense part and
- * g already holds the world's summed dense gradient (the caller's RCCL all-reduce). */
+ * g already holds the world's summed dense gradient (the caller's RCCL all-reduce).  D >= 4 * world, else AMID_ERR_UNSUPPORTED: lane r of
+ * a half-wave hands rank r's row index to the column loop, in which only the first D / 4 lanes are alive, and a shuffle from a lane that is
+ * switched off reads index 0 -- the wrong rank's row.  The padding (rows past a rank's count, the tail of the id rows, the slack
+ * behind the dense part) is never read. */
 int amid_optimizer_step_gathered_f32(float* p, float* m, float* v, float* g, long long n, float* table, float* m_tab, float* v_tab,
                                      int* last, const float* gathered, int world, int umax, long long chunk_floats, int id_rows,
                                      long long dense_off, int D, int sentinel, float grad_scale, const void* step_state, void* stream);
