@@ -412,6 +412,24 @@ extern "C" int amid_attn_bwd_live_f32(const float* q, const float* k, const floa
     return amid_attn_mfma_bwd_launch(&a, stream);
 }
 
+// the long causal shape (attention_mfma_long.hip: head dim 16, 64 < T <= 256) over a live list, inference form: no dropout, no statistics --
+// the evaluation batch's attention core beyond 64 tokens.  live = NULL: every sequence of both domains.  Every row written is the bits
+// amid_attn_fwd_f32(..., train = 0) writes there.
+int amid_attn_long_live_infer_launch(const void* args, void* stream);
+extern "C" int amid_attn_long_live_supported(int T, int D, int H) {
+    return (T > 64 && T <= 256 && H > 0 && H <= 8 && H % 4 == 0 && D == 16 * H) ? 1 : 0;
+}
+extern "C" int amid_attn_fwd_long_live_infer_f32(const float* q, const float* k, const float* v, int B, int T, int D, int H, float* o,
+                                                 const int* live, void* stream) {
+    AMID_CHECK_ARG(q && k && v && o && B > 0 && T > 0 && D > 0 && H > 0);
+    if (!amid_attn_long_live_supported(T, D, H)) return AMID_ERR_UNSUPPORTED;
+    AttnArgs a = {};
+    if (int e = attn_fill(a, q, k, v, nullptr, B, T, D, H, 1, 0, nullptr, 0, 0.f)) return e;
+    a.o = o; a.stats = nullptr; a.live = live;
+    if (!long_shape(a)) return AMID_ERR_UNSUPPORTED;
+    return amid_attn_long_live_infer_launch(&a, stream);
+}
+
 // ... and the BERT4Rec shape (bidirectional, key mask from seq_d2 > 0 for both encoders, 4 heads of 32, T <= 64: attention_mfma_bert.hip)
 // over a live list: nothing of the other sequences is read or written
 extern "C" int amid_attn_bert_live_supported(int T, int D, int H) { return (T > 0 && T <= 64 && H == 4 && D == 128) ? 1 : 0; }

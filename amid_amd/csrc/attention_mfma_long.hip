@@ -35,18 +35,21 @@ __device__ __forceinline__ unsigned long long row_keep_word_blk(unsigned long lo
     return w;
 }
 
-__global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
+// the forward of sequence `seq` (= g * B + b), heads part * hw .. of it.  INFER: the inference form -- no dropout is drawn (every key
+// kept, no rescale) and no statistics are stored; the arithmetic that remains is the other form's with train = 0, operation for operation
+template <bool INFER>
+__device__ __forceinline__ void attn_fwd_long_seq(const AttnArgs& a, int seq, int part) {
     const int T = a.T, D = a.D, H = a.H;
-    const int hw = blockDim.x >> 6, parts = H / hw;
-    const int seq = blockIdx.x / parts, part = blockIdx.x - seq * parts, g = seq / a.B, b = seq - g * a.B;
+    const int hw = blockDim.x >> 6;
+    [[maybe_unused]] const int g = seq / a.B, b = seq - g * a.B;
     const long long rowbase = (long long)seq * T;
     const int h = part * hw + wave_id(), lane = lane_id();
     const int m = lane & 15, gq = lane >> 4;
     const int NB = (T + 63) >> 6;
     const int col4 = h * AHD + 4 * gq, colm = h * AHD + m;
-    unsigned long long seed = 0; unsigned step = 0;
-    if (a.train) { seed = a.st->seed; step = (unsigned)a.st->step; }
-    const unsigned site = site_id(g, a.layer, SITE_ATTN);
+    [[maybe_unused]] unsigned long long seed = 0; [[maybe_unused]] unsigned step = 0;
+    if constexpr (!INFER) { if (a.train) { seed = a.st->seed; step = (unsigned)a.st->step; } }
+    [[maybe_unused]] const unsigned site = site_id(g, a.layer, SITE_ATTN);
     for (int qb = 0; qb < NB; ++qb) {
         float4 qfr[4];
         float mx[4], l[4];
@@ -56,7 +59,7 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
             qfr[qi] = f4scale(ld4_row(a.q, rowbase, qb * 64 + qi * 16 + m, T, D, col4), a.scale);
             mx[qi] = -INFINITY; l[qi] = 0.f; oacc[qi] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        const int qrow_own = min(qb * 64 + gq * 16 + m, T - 1);           // lane (m, gq) generates the keep words of this query row
+        [[maybe_unused]] const int qrow_own = min(qb * 64 + gq * 16 + m, T - 1);           // lane (m, gq) generates the keep words of this query row
         for (int kb = 0; kb <= qb; ++kb) {
             const bool diag = kb == qb;
             float4 kf[4];
@@ -67,12 +70,15 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) vt[kj][r] = ld1_row(a.v, rowbase, kb * 64 + kj * 16 + 4 * gq + r, T, D, colm);
             }
-            unsigned long long kw_own = ~0ull;
-            if (a.train) kw_own = row_keep_word_blk(seed, site, step, (unsigned long long)(b * H + h) * T + qrow_own, T, a.thr16, kb);
+            [[maybe_unused]] unsigned long long kw_own = ~0ull;
+            if constexpr (!INFER) {
+                if (a.train) kw_own = row_keep_word_blk(seed, site, step, (unsigned long long)(b * H + h) * T + qrow_own, T, a.thr16, kb);
+            }
 #pragma unroll
             for (int qi = 0; qi < 4; ++qi) {
                 const int q = qb * 64 + qi * 16 + m;
-                const unsigned long long kw = shfl64(kw_own, qi * 16 + m);
+                [[maybe_unused]] unsigned long long kw = ~0ull;
+                if constexpr (!INFER) kw = shfl64(kw_own, qi * 16 + m);
                 f32x4 s[4];
                 float bm = -INFINITY;
 #pragma unroll
@@ -101,7 +107,8 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
                             const int nl = kj * 16 + 4 * gq + r;
                             const float p = fast_exp(s[kj][r] - mnew);
                             lb += p;
-                            const float pd = ((kw >> nl) & 1ull) ? p * a.dscale : 0.f;
+                            float pd = p;                          // (train = 0: every key kept, dscale = 1)
+                            if constexpr (!INFER) pd = ((kw >> nl) & 1ull) ? p * a.dscale : 0.f;
                             ob = mfma4(vt[kj][r], pd, ob);
                         }
                     }
@@ -118,13 +125,31 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
             if (q < T) {
                 const float rl = 1.0f / l[qi];
                 st4(a.o + (rowbase + q) * D + col4, make_float4(oacc[qi][0] * rl, oacc[qi][1] * rl, oacc[qi][2] * rl, oacc[qi][3] * rl));
-                if (gq == 0 && a.stats) {
-                    float* sp = a.stats + ((rowbase + q) * H + h) * 2;
-                    sp[0] = mx[qi]; sp[1] = rl;
+                if constexpr (!INFER) {
+                    if (gq == 0 && a.stats) {
+                        float* sp = a.stats + ((rowbase + q) * H + h) * 2;
+                        sp[0] = mx[qi]; sp[1] = rl;
+                    }
                 }
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnArgs a) {
+    const int parts = a.H / (blockDim.x >> 6);
+    const int seq = blockIdx.x / parts;
+    attn_fwd_long_seq<false>(a, seq, blockIdx.x - seq * parts);
+}
+
+// the inference form over a live list (AttnArgs::live; nullptr: every sequence of both domains): a workgroup takes slot blockIdx.x / parts
+// of the list -- slot j < live[B]: sequence (0, live[j]), else (1, live[j]); nothing of the other sequences is read or written
+__global__ __launch_bounds__(256) void attn_fwd_long_live_infer_kernel(const AttnArgs a) {
+    const int parts = a.H / (blockDim.x >> 6);
+    int seq = blockIdx.x / parts;
+    const int part = blockIdx.x - seq * parts;
+    if (a.live != nullptr) seq = (seq >= a.live[a.B] ? a.B : 0) + a.live[seq];
+    attn_fwd_long_seq<true>(a, seq, part);
 }
 
 __global__ __launch_bounds__(256) void attn_bwd_long_kernel(const AttnArgs a) {
@@ -274,6 +299,14 @@ int amid_attn_long_fwd_launch(const void* args, void* stream) {
     const AttnArgs a = *(const AttnArgs*)args;
     const int hw = 4, grid = 2 * a.B * (a.H / hw);
     attn_fwd_long_kernel<<<grid, hw * 64, 0, (hipStream_t)stream>>>(a);
+    AMID_LAUNCH_CHECK();
+    return AMID_OK;
+}
+
+int amid_attn_long_live_infer_launch(const void* args, void* stream) {
+    const AttnArgs a = *(const AttnArgs*)args;
+    const int hw = 4, grid = (a.live != nullptr ? 1 : 2) * a.B * (a.H / hw);
+    attn_fwd_long_live_infer_kernel<<<grid, hw * 64, 0, (hipStream_t)stream>>>(a);
     AMID_LAUNCH_CHECK();
     return AMID_OK;
 }

@@ -113,7 +113,50 @@ __global__ __launch_bounds__(STRIP_THREADS) void strip_qkv_fwd_kernel(const Stri
     qkv_fwd_chain<D, false>(a, sg, ring, row, t.g, X, lw, lb);
 }
 
-template <int D, bool NEXT>
+// Layer 0's q / k / v with the gather K1 as the strip's prologue (evaluation batches: no K1 launch, no round trip of the gathered rows):
+// lane (m, g) builds its 16 bytes of the row in every column tile -- x = table[idx[row]] + pos[domain][t], the "== 0" bits, masked elements
+// zeroed: embed.hip embed_fwd_kernel's arithmetic in eval mode (no dropout), operation for operation, so the same bits -- keeps them as the
+// chain's input and writes the mask bytes where K1 puts them (the later strips of the batch read them); x itself is not stored.
+struct StripGatherArgs { const float* table; const int* idx; const float* pos[2]; unsigned char* tmq; };
+
+template <int D>
+__global__ __launch_bounds__(STRIP_THREADS) void strip_qkv_fwd_gather_kernel(const StripQkvArgs a, const StripGatherArgs ga, const StripGeom sg) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    Ring<D> ring(smem);
+    ring.first(a.w_in[strip_domain(blockIdx.x)] + 1LL * D * D);
+    const StripTile t = strip_tile(sg, blockIdx.x);
+    if (!t.live) { w_ring_wait(); return; }
+    const StripRow row = strip_row<D>(sg, t);
+    StripRegs<D> X;
+    ColVec<D> lw, lb;
+    {
+        const int gq = lane_id() >> 4;
+        const int id = ga.idx[(long long)t.g * sg.M + row.local];             // (a lane past the domain's rows re-reads the tile's first row)
+        const float* __restrict__ trow = ga.table + (long long)id * D;
+        const float* __restrict__ prow = ga.pos[t.g] + (long long)(row.local % sg.T) * D;
+        const GBuf gtm(ga.tmq, sg.tm_bytes);
+        const unsigned tbase = row.ok ? (row.off - 16u * (unsigned)gq) >> 4 : STRIP_OOB;      // row * D / 4 bytes
+#pragma unroll
+        for (int ct = 0; ct < D / 16; ++ct) {
+            const int col = ct * 16 + 4 * gq;
+            const float4 tv = ld4_global(trow + col), pv = ld4_global(prow + col);
+            float4 x = make_float4(tv.x + pv.x, tv.y + pv.y, tv.z + pv.z, tv.w + pv.w);
+            const unsigned bits = (x.x == 0.f ? 1u : 0u) | (x.y == 0.f ? 2u : 0u) | (x.z == 0.f ? 4u : 0u) | (x.w == 0.f ? 8u : 0u);
+            if (bits & 1u) x.x = 0.f;
+            if (bits & 2u) x.y = 0.f;
+            if (bits & 4u) x.z = 0.f;
+            if (bits & 8u) x.w = 0.f;
+            X.v[ct] = row.ok ? f32x4{x.x, x.y, x.z, x.w} : f32x4{0.f, 0.f, 0.f, 0.f};      // (rows past the domain: zeros, as a strip_load gives)
+            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bits, gtm.r, row.ok ? (int)(tbase + (unsigned)(ct * 4 + gq)) : (int)STRIP_OOB, 0, 0);
+        }
+    }
+    lw.load(a.ln_w[t.g]); lb.load(a.ln_b[t.g]);
+    qkv_fwd_chain<D, false>(a, sg, ring, row, t.g, X, lw, lb);
+}
+
+// SAVE = false: the inference form -- r, y, h and the next layer's input x', which only a backward reads, are not stored; what the next
+// launch reads (x' of the last layer; qn, q, k, v of the next one) is computed by the same operations: the same bits
+template <int D, bool NEXT, bool SAVE = true>
 __global__ __launch_bounds__(STRIP_THREADS) void strip_oproj_ffn_fwd_kernel(const StripOffArgs a, const StripQkvArgs nx, const StripGeom sg) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NT = D / 16;
@@ -148,7 +191,10 @@ __global__ __launch_bounds__(STRIP_THREADS) void strip_oproj_ffn_fwd_kernel(cons
         const float* buf = ring.next();
         bias.load(a.b1[g]);
         strip_zero<D>(acc);
-        strip_mma<D>(acc, Y, buf, [&](int ct, int j) { ring.fetch(a.w2[g], ct, j); store_spread<D>(gr, row, R, ct, j); });
+        strip_mma<D>(acc, Y, buf, [&](int ct, int j) {
+            ring.fetch(a.w2[g], ct, j);
+            if constexpr (SAVE) store_spread<D>(gr, row, R, ct, j);
+        });
         add_bias<D>(acc, bias);
         to_regs<D>(H, acc);
         if (a.train) strip_dropout<D>(H, seed, site_id(g, a.layer, SITE_FFN1), step, row.local, a.spec, a.scale);
@@ -164,8 +210,10 @@ __global__ __launch_bounds__(STRIP_THREADS) void strip_oproj_ffn_fwd_kernel(cons
         strip_zero<D>(acc);
         strip_mma<D>(acc, H, buf, [&](int ct, int j) {
             if constexpr (NEXT) ring.fetch(nx.w_in[g] + 1LL * D * D, ct, j);
-            store_spread<D>(gy, row, Y, ct, j);
-            if (ct < NT / 2 && (j & 3) == 3) strip_store_ct<D>(gh, row, H, 2 * ct + (j >> 2));
+            if constexpr (SAVE) {
+                store_spread<D>(gy, row, Y, ct, j);
+                if (ct < NT / 2 && (j & 3) == 3) strip_store_ct<D>(gh, row, H, 2 * ct + (j >> 2));
+            }
         });
         add_bias<D>(acc, bias);
         to_regs<D>(A, acc);
@@ -175,7 +223,7 @@ __global__ __launch_bounds__(STRIP_THREADS) void strip_oproj_ffn_fwd_kernel(cons
         if (has_tm) strip_apply_tm<D>(A, tm);
     }
     if constexpr (NEXT) {
-        qkv_fwd_chain<D, true>(nx, sg, ring, row, g, A, lw, lb);
+        qkv_fwd_chain<D, SAVE>(nx, sg, ring, row, g, A, lw, lb);
     } else {
         strip_store<D>(gxo, row, A);
     }
@@ -588,6 +636,59 @@ extern "C" int amid_sas_strip_oproj_ffn_fwd_f32(const float* o, const float* qn,
     if (D == 64 && next) return launch_strip<strip_oproj_ffn_fwd_kernel<64, true>, 64>(sg, stream, a, nx);
     if (D == 64) return launch_strip<strip_oproj_ffn_fwd_kernel<64, false>, 64>(sg, stream, a, nx);
     return AMID_ERR_UNSUPPORTED;
+}
+
+// ---- the evaluation batch's strip launches (inference forms; SasrecEngine._enqueue_eval_encoders beyond 64 tokens) ----
+extern "C" int amid_sas_strip_infer_supported(int T, int D) { return (T > 0 && (D == 128 || D == 64)) ? 1 : 0; }
+
+extern "C" int amid_sas_strip_qkv_fwd_gather_infer_f32(const float* table, const int* idx_all, const float* pos0, const float* pos1,
+                                                       const float* const* ln_w, const float* const* ln_b, const float* const* w_in,
+                                                       const float* const* b_in, float ln_eps, int B, int T, int D, const int* live,
+                                                       unsigned char* tmq, float* qn, float* q, float* k, float* v, void* stream) {
+    AMID_CHECK_ARG(table && idx_all && pos0 && pos1 && ln_w && ln_b && w_in && b_in && tmq && qn && q && k && v && B > 0 && T > 0 && D > 0);
+    for (int g = 0; g < 2; ++g) AMID_CHECK_ARG(ln_w[g] && ln_b[g] && w_in[g] && b_in[g]);
+    if (!amid_sas_strip_infer_supported(T, D)) return AMID_ERR_UNSUPPORTED;
+    StripQkvArgs a;
+    a.x = nullptr; a.qn = qn; a.q = q; a.k = k; a.v = v; a.ln_eps = ln_eps;
+    for (int g = 0; g < 2; ++g) { a.ln_w[g] = ln_w[g]; a.ln_b[g] = ln_b[g]; a.w_in[g] = w_in[g]; a.b_in[g] = b_in[g]; }
+    StripGatherArgs ga;
+    ga.table = table; ga.idx = idx_all; ga.pos[0] = pos0; ga.pos[1] = pos1; ga.tmq = tmq;
+    StripGeom sg;
+    if (int e = make_strip_geom(B, T, D, live, &sg)) return e;
+    if (D == 128) return launch_strip<strip_qkv_fwd_gather_kernel<128>, 128>(sg, stream, a, ga);
+    return launch_strip<strip_qkv_fwd_gather_kernel<64>, 64>(sg, stream, a, ga);
+}
+
+extern "C" int amid_sas_strip_oproj_ffn_fwd_infer_f32(const float* o, const float* qn, const float* const* w_o, const float* const* b_o,
+                                                      const float* const* ln_w, const float* const* ln_b, const float* const* w1,
+                                                      const float* const* b1, const float* const* w2, const float* const* b2,
+                                                      const unsigned char* tmq, float ln_eps, int B, int T, int D, const int* live, float* xo,
+                                                      const float* const* nln_w, const float* const* nln_b, const float* const* nw_in,
+                                                      const float* const* nb_in, float* nqn, float* nq, float* nk, float* nv, void* stream) {
+    AMID_CHECK_ARG(o && qn && w_o && b_o && ln_w && ln_b && w1 && b1 && w2 && b2 && B > 0 && T > 0 && D > 0);
+    const bool next = nln_w != nullptr;
+    AMID_CHECK_ARG(next ? (nln_b && nw_in && nb_in && nqn && nq && nk && nv) : xo != nullptr);
+    for (int g = 0; g < 2; ++g) {
+        AMID_CHECK_ARG(w_o[g] && b_o[g] && ln_w[g] && ln_b[g] && w1[g] && b1[g] && w2[g] && b2[g]);
+        AMID_CHECK_ARG(!next || (nln_w[g] && nln_b[g] && nw_in[g] && nb_in[g]));
+    }
+    if (!amid_sas_strip_infer_supported(T, D)) return AMID_ERR_UNSUPPORTED;
+    StripOffArgs a;
+    a.o = o; a.qn = qn; a.tmq = tmq; a.r = nullptr; a.y = nullptr; a.h = nullptr; a.xo = xo; a.ln_eps = ln_eps;
+    a.st = nullptr; a.layer = 0; a.train = 0; a.spec = drop_spec(0.f); a.scale = 1.0f;
+    StripQkvArgs nx = {};
+    for (int g = 0; g < 2; ++g) {
+        a.w_o[g] = w_o[g]; a.b_o[g] = b_o[g]; a.ln_w[g] = ln_w[g]; a.ln_b[g] = ln_b[g];
+        a.w1[g] = w1[g]; a.b1[g] = b1[g]; a.w2[g] = w2[g]; a.b2[g] = b2[g];
+        if (next) { nx.ln_w[g] = nln_w[g]; nx.ln_b[g] = nln_b[g]; nx.w_in[g] = nw_in[g]; nx.b_in[g] = nb_in[g]; }
+    }
+    if (next) { nx.x = nullptr; nx.qn = nqn; nx.q = nq; nx.k = nk; nx.v = nv; nx.ln_eps = ln_eps; }
+    StripGeom sg;
+    if (int e = make_strip_geom(B, T, D, live, &sg)) return e;
+    if (D == 128 && next) return launch_strip<strip_oproj_ffn_fwd_kernel<128, true, false>, 128>(sg, stream, a, nx);
+    if (D == 128) return launch_strip<strip_oproj_ffn_fwd_kernel<128, false, false>, 128>(sg, stream, a, nx);
+    if (next) return launch_strip<strip_oproj_ffn_fwd_kernel<64, true, false>, 64>(sg, stream, a, nx);
+    return launch_strip<strip_oproj_ffn_fwd_kernel<64, false, false>, 64>(sg, stream, a, nx);
 }
 
 static void fill_ffn_bwd(StripFfnBwdArgs& a, const float* dxo, const unsigned char* tmq, const float* h, const float* r,

@@ -1421,7 +1421,18 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
     #           rows, D 64 / 128: five launches; other batches: amid_itc_mix_fwd_f32 in front of it, the head reading pl.u).
     #   isInC:  marshal + enqueue_forward's own gather / token group / encoder launches over the 2T-token rows (gather_items=False,
     #           head=False), then amid_eval_head_f32 on pl.x[2] (+ isDR: amid_lnmean_fwd_f32 and amid_eval_head_u_f32).
+    #   beyond 64 tokens (plain, isDR, isItC; fp32, D 128, 64 < T <= 256: _eval_long): the one-launch forward does not reach there, so the
+    #           encoder is seven launches on the strip kernels' inference forms -- marshal, layer 0's q / k / v gathering its own rows (no K1),
+    #           the long attention core over the live list, out-projection / feed-forward + layer 1's q / k / v, attention, out-projection /
+    #           feed-forward, the head -- each the arithmetic enqueue_forward(train=False) runs for the shape, over the live rows only.
     EVAL_FUSED = True
+    EVAL_LONG = True           # ... also at 64 < T <= 256 (False: those shapes evaluate through enqueue_forward, as before)
+
+    def _eval_long(self, pl: SasrecPlan) -> bool:
+        """Whether the evaluation batch's encoders are the strip launches' inference forms around the long attention core's live form."""
+        shp, L = pl.shape, lib()
+        return bool(self.EVAL_LONG and pl.strip and self.compute == "f32" and self._ceff() != "bf16" and self.D == 128 and not self.inc_bs
+                    and L.value("amid_attn_long_live_supported", shp.Tenc, self.D, self.H) and L.value("amid_sas_strip_infer_supported", shp.Tenc, self.D))
 
     def eval_fused_ok(self, pl: SasrecPlan) -> bool:
         shp = pl.shape
@@ -1431,7 +1442,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             return False
         if self.inc_bs:          # the encoders are enqueue_forward's for any shape; the head's own limits (amid_eval_head_f32)
             return bool(self.D % 32 == 0 and self.D <= 128 and 0 < self.hid <= 64 and self.hid % 4 == 0)
-        return bool(pl.strip and self.SEQ_FORWARD and lib().value("amid_sas_seq_supported", shp.B, shp.Tenc, self.D, self.H))
+        return bool((pl.strip and self.SEQ_FORWARD and lib().value("amid_sas_seq_supported", shp.B, shp.Tenc, self.D, self.H)) or self._eval_long(pl))
 
     def _eval_out(self, pl: SasrecPlan):
         """The batch's results, one int32 image [rank B | rank_raw B | loss_part B (fp32 bits)] (+ the scores, for tests)."""
@@ -1501,6 +1512,9 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         fp, st = self.dense, self.step_state.data_ptr()
         lf = None if self.itc_bs else pl.live.data_ptr()      # isItC: the pair-max reads both domains' rows of every sample
         pos = (fp.ptr("sac1.pos_emb.weight"), fp.ptr("sac2.pos_emb.weight"))
+        if not L.value("amid_sas_seq_supported", B, T, D, self.H):       # eval_fused_ok said yes: the long shape (_eval_long)
+            self._enqueue_eval_encoders_long(pl, lf, pos)
+            return
         split = self._fwd_on_pieces(pl, B, T)
         pl.w16_written = pl.wT16x3_written = False
         # the forward's workgroups gather their own rows: three launches a batch (the gather prologue walks a live list: not without one)
@@ -1550,6 +1564,25 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             else:
                 L.call("amid_sas_seq_fwd_f32", 2, tl(pl.x[:2]), pl.x[2].data_ptr(), *c, *saved, pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, self.H,
                        lf, st, 0, SASREC_P_DROP, s)
+
+    def _enqueue_eval_encoders_long(self, pl: SasrecPlan, lf, pos) -> None:
+        """64 < T <= 256: six launches up to pl.x[2], in the plan's q / k / v / o buffers; no gathered rows, nothing saved for a backward."""
+        L, s, shp, D = lib(), self.s, pl.shape, self.D
+        B, T = shp.B, shp.Tenc
+        pre = "sac{d}"
+        lay = lambda l, names: tuple(self._pp(f"{pre}.{n}".replace("#", str(l))) for n in names)      # noqa: E731
+        qkv_n = ("attention_layernorms.#.weight", "attention_layernorms.#.bias", "attention_layers.#.in_proj_weight", "attention_layers.#.in_proj_bias")
+        rest_n = ("attention_layers.#.out_proj.weight", "attention_layers.#.out_proj.bias", "forward_layernorms.#.weight", "forward_layernorms.#.bias",
+                  "forward_layers.#.conv1.weight", "forward_layers.#.conv1.bias", "forward_layers.#.conv2.weight", "forward_layers.#.conv2.bias")
+        out = lambda l: (pl.qn[l].data_ptr(), pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr())      # noqa: E731
+        L.call("amid_sas_strip_qkv_fwd_gather_infer_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), *pos, *lay(0, qkv_n), SASREC_LN_EPS, B, T, D,
+               lf, pl.tmq.data_ptr(), *out(0), s)
+        for l in (0, 1):
+            L.call("amid_attn_fwd_long_live_infer_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), B, T, D, self.H,
+                   pl.o[l].data_ptr(), lf, s)
+            nxt = (*lay(1, qkv_n), *out(1)) if l == 0 else (None,) * 8
+            L.call("amid_sas_strip_oproj_ffn_fwd_infer_f32", pl.o[l].data_ptr(), pl.qn[l].data_ptr(), *lay(l, rest_n), pl.tmq.data_ptr(),
+                   SASREC_LN_EPS, B, T, D, lf, None if l == 0 else pl.x[2].data_ptr(), *nxt, s)
 
     def capture_eval(self, pl: SasrecPlan, fix_value: float, with_loss: bool = True) -> None:
         """The evaluation batch as a hipGraph over the plan's static inputs (parameters are read at replay time and the forward's weight

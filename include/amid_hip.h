@@ -708,6 +708,14 @@ int amid_attn_fwd_live_f32(const float* q, const float* k, const float* v, int B
 int amid_attn_bwd_live_f32(const float* q, const float* k, const float* v, const float* o, const float* stats, const float* d_o, int B,
                            int T, int D, int H, int causal, int layer, const void* step_state, int train, float p_drop, float* dq,
                            float* dk, float* dv, const int* live, void* stream);
+/* The long causal shape (csrc/attention_mfma_long.hip: head dim 16, 64 < T <= 256, H 4 or 8) over a live list, INFERENCE form: the
+ * evaluation batch's attention core beyond 64 tokens.  No dropout is drawn and no statistics are stored; live as amid_attn_fwd_live_f32
+ * reads it, NULL = every sequence of both domains.  Every row written is bit-identical to amid_attn_fwd_f32(..., causal = 1, train = 0) on
+ * the same q, k, v; rows of other sequences are not written.  amid_attn_long_live_supported: 1 when the entry covers (T, D, H); other
+ * shapes return AMID_ERR_UNSUPPORTED, null or non-positive arguments AMID_ERR_ARG, before any device call. */
+int amid_attn_long_live_supported(int T, int D, int H);
+int amid_attn_fwd_long_live_infer_f32(const float* q, const float* k, const float* v, int B, int T, int D, int H, float* o, const int* live,
+                                      void* stream);
 int amid_head_fwd_bwd_own_f32(const float* x, const float* const* ln_w, const float* const* ln_b, const float* items, const float* w1,
                               const float* b1, const float* w2, const float* b2, const float* labels, const long long* domain_id, int B,
                               int T, int NI, int D, int hid, float eps, float* u, float* p1, float* p2, float* dp1, float* dp2,
@@ -735,6 +743,27 @@ int amid_sas_strip_oproj_ffn_fwd_f32(const float* o, const float* qn, const floa
                                      int D, const int* live, int layer, const void* step_state, int train, float p_drop, float* r, float* y,
                                      float* h, float* xo, const float* const* nln_w, const float* const* nln_b, const float* const* nw_in,
                                      const float* const* nb_in, float* nqn, float* nq, float* nk, float* nv, void* stream);
+/* INFERENCE forms of the two forward strip launches (the evaluation batch beyond 64 tokens, SasrecEngine._enqueue_eval_encoders): eval mode,
+ * nothing stored that only a backward reads.  amid_sas_strip_infer_supported: 1 for T > 0 and D 64 / 128 (other shapes: AMID_ERR_UNSUPPORTED;
+ * null or non-positive arguments: AMID_ERR_ARG; both before any device call).
+ * amid_sas_strip_qkv_fwd_gather_infer_f32: layer 0's amid_sas_strip_qkv_fwd_f32 forming its own input rows -- x = table[idx_all[row]] +
+ * pos[domain][t] with the "== 0" elements zeroed, K1's arithmetic in eval mode -- and writing the "== 0" mask bytes tmq [2 B T, D / 4] the
+ * later strips read; x is not stored.  qn, q, k, v and tmq are bit-identical to amid_embed_fwd_live_f32 (live = NULL: amid_embed_fwd_f32)
+ * with train = 0 followed by amid_sas_strip_qkv_fwd_f32.  idx_all: [seq_d1 (B T) | seq_d2 (B T) | ...] int32, range-checked by the caller's
+ * packing launch. */
+int amid_sas_strip_infer_supported(int T, int D);
+int amid_sas_strip_qkv_fwd_gather_infer_f32(const float* table, const int* idx_all, const float* pos0, const float* pos1,
+                                            const float* const* ln_w, const float* const* ln_b, const float* const* w_in,
+                                            const float* const* b_in, float ln_eps, int B, int T, int D, const int* live, unsigned char* tmq,
+                                            float* qn, float* q, float* k, float* v, void* stream);
+/* amid_sas_strip_oproj_ffn_fwd_f32 with train = 0 that stores neither r, y, h nor -- with the next layer's q / k / v epilogue (nln_w != NULL;
+ * xo may then be NULL) -- the layer output: xo (without the epilogue) and nqn, nq, nk, nv (with it) are bit-identical to that entry's. */
+int amid_sas_strip_oproj_ffn_fwd_infer_f32(const float* o, const float* qn, const float* const* w_o, const float* const* b_o,
+                                           const float* const* ln_w, const float* const* ln_b, const float* const* w1,
+                                           const float* const* b1, const float* const* w2, const float* const* b2, const unsigned char* tmq,
+                                           float ln_eps, int B, int T, int D, const int* live, float* xo, const float* const* nln_w,
+                                           const float* const* nln_b, const float* const* nw_in, const float* const* nb_in, float* nqn,
+                                           float* nq, float* nk, float* nv, void* stream);
 /* The backward strip entry points (and amid_sas_seq_bwd_f32) take mma_bf16: 1 = the data-gradient products on
  * v_mfma_f32_16x16x32_bf16 (operands rounded to bf16, fp32 accumulation, everything else fp32; D = 128) -- the w*T pointer arguments then
  * hold the bf16 fragment images of the TRANSPOSED weights (amid_sas_weights_bf16(..., transposed = 1, ...), 2 D D bytes each) instead of
