@@ -53,21 +53,62 @@ def _ctype_of(decl: str):
     return _SCALARS[d]
 
 
-def parse_header(path: str = HEADER_PATH) -> Dict[str, Tuple[object, List[object]]]:
-    text = open(path).read()
+def parse_prototypes(text: str) -> Dict[str, Tuple[object, List[object], List[str]]]:
+    """Entry point -> (ctypes return type, ctypes parameter types, parameter names) for every ``amid_*`` prototype in `text`."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)      # drop comments
     text = re.sub(r"//[^\n]*", " ", text)
-    protos: Dict[str, Tuple[object, List[object]]] = {}
+    protos: Dict[str, Tuple[object, List[object], List[str]]] = {}
     for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(amid_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
         ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
-        argtypes = []
+        argtypes, names = [], []
         if args and args != "void":
             for a in args.split(","):
                 a = a.strip()
-                mm = re.match(r"^(.*?)([A-Za-z_]\w*)$", a, flags=re.S)   # strip the parameter name
+                mm = re.match(r"^(.*?)([A-Za-z_]\w*)$", a, flags=re.S)   # the declaration, the parameter name
                 argtypes.append(_ctype_of(mm.group(1)))
-        protos[name] = (_ctype_of(ret), argtypes)
+                names.append(mm.group(2))
+        protos[name] = (_ctype_of(ret), argtypes, names)
     return protos
+
+
+def parse_header(path: str = HEADER_PATH) -> Dict[str, Tuple[object, List[object], List[str]]]:
+    return parse_prototypes(open(path).read())
+
+
+class Binder:
+    """Named arguments -> the positional order of a prototype.  The values come from `tables` (mappings parameter name -> value: the
+    engines' named pointer tables; names the entry point does not take are ignored, which is how one table serves entry points that
+    take a subset of it) and from `args` (every name must be a parameter).  Every parameter must be supplied exactly once -- null is
+    an explicit None --, otherwise TypeError naming the entry point and the parameter: nothing is launched.  The order is resolved once
+    per (entry point, names supplied by each source); after that a bind is one tuple build."""
+
+    def __init__(self, protos) -> None:
+        self._params = {entry: tuple(p[2]) for entry, p in protos.items()}
+        self._orders: Dict[tuple, list] = {}
+
+    def bind(self, entry: str, tables, args) -> tuple:
+        key = (entry, tuple(map(tuple, tables)), tuple(args))
+        order = self._orders.get(key)
+        if order is None:
+            order = self._orders[key] = self._resolve(entry, tables, args)
+        srcs = (*tables, args)
+        return tuple([srcs[i][n] for i, n in order])
+
+    def _resolve(self, entry: str, tables, args) -> list:
+        params = self._params.get(entry)
+        if params is None:
+            raise TypeError(f"{entry} is not declared in include/amid_hip.h")
+        for n in args:
+            if n not in params:
+                raise TypeError(f"{entry} has no parameter {n!r}")
+        order = []
+        for n in params:
+            at = [i for i, src in enumerate((*tables, args)) if n in src]
+            if len(at) != 1:
+                raise TypeError(f"{entry}: parameter {n!r} " + ("is not supplied (null is an explicit None)" if not at else
+                                                               f"is supplied {len(at)} times"))
+            order.append((at[0], n))
+        return order
 
 
 def declared_symbols() -> List[str]:
@@ -86,7 +127,9 @@ class _Lib:
             raise AmidLibraryError(f"cannot load {LIB_PATH}: {e}") from e
         self._fn = {}
         self.timer = None          # optional KernelTimer (bench.py): HIP events around every launch
-        for name, (restype, argtypes) in parse_header().items():
+        protos = parse_header()
+        self._binder = Binder(protos)
+        for name, (restype, argtypes, _) in protos.items():
             try:
                 f = getattr(self._dll, name)
             except AttributeError as e:
@@ -106,6 +149,11 @@ class _Lib:
         if code != 0:
             text = self._fn["amid_error_string"](code)
             raise AmidError(name, code, text.decode() if text else "?")
+
+    def call_named(self, name: str, *tables, **args) -> None:
+        """call() with the arguments given by parameter name (Binder): the wide launches' form.  The header's parameter names are
+        part of what this relies on."""
+        return self.call(name, *self._binder.bind(name, tables, args))
 
     def value(self, name: str, *args):
         """Call an entry point that returns a plain value (sizes, counts)."""

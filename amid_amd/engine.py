@@ -30,6 +30,17 @@ from .engine_io import InputMixin
 from .plan import (DR_HEADS, SASREC_HEADS, SASREC_LN_EPS, SASREC_P_DROP, FlatParams, SasrecPlan, Shape,      # noqa: F401  (re-exported)
                    sasrec_dense_names)
 
+# The twelve parameter families of an encoder layer: (parameter name in include/amid_hip.h, state_dict name behind "sac{d}.").  The first
+# four feed the layer's q / k / v launch, the other eight its out-projection / feed-forward launch.  THE list: every table derives from it.
+SASREC_FAMILIES = (("ln1_w", "attention_layernorms.{l}.weight"), ("ln1_b", "attention_layernorms.{l}.bias"),
+                   ("w_in", "attention_layers.{l}.in_proj_weight"), ("b_in", "attention_layers.{l}.in_proj_bias"),
+                   ("w_o", "attention_layers.{l}.out_proj.weight"), ("b_o", "attention_layers.{l}.out_proj.bias"),
+                   ("ln2_w", "forward_layernorms.{l}.weight"), ("ln2_b", "forward_layernorms.{l}.bias"),
+                   ("w1", "forward_layers.{l}.conv1.weight"), ("b1", "forward_layers.{l}.conv1.bias"),
+                   ("w2", "forward_layers.{l}.conv2.weight"), ("b2", "forward_layers.{l}.conv2.bias"))
+QKV_FAMILIES = tuple(n for n, _ in SASREC_FAMILIES[:4])
+FFN_FAMILIES = tuple(n for n, _ in SASREC_FAMILIES[4:])
+
 
 class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
     """Parameters, optimizer state and launch sequences for SASRec (isInC = isItC = isDR = False)."""
@@ -201,25 +212,88 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
     # ------------------------------------------------------------------ pointer helpers
     def _pp(self, fmt: str, buf: Optional[torch.Tensor] = None, extra: int = 0):
         """Host array (domain 0, domain 1) of device pointers of a per-domain parameter."""
-        key = (fmt, 0 if buf is None else buf.data_ptr(), extra)
-        c = self._ptr_cache.get(key)
-        if c is None:
-            c = ptr_array([self.dense.ptr(fmt.format(d=d), buf, extra) for d in (1, 2)])
-            self._ptr_cache[key] = c
-        return c
+        return self._cached((fmt, 0 if buf is None else buf.data_ptr(), extra),
+                            lambda: ptr_array([self.dense.ptr(fmt.format(d=d), buf, extra) for d in (1, 2)]))
 
     def _wT(self, layer: int, which: int):
         """Host array (domain 0, domain 1) of the transposed projection weight `which` (q, k, v, o, c1, c2) of `layer`: fp32 transposes,
         or -- pl.strip with compute = "bf16" -- their bf16 fragment images (amid_sas_weights_bf16, refreshed by enqueue_backward)."""
         bf = self._bf16_bwd
         p3 = self._p3_bwd
-        key = ("wT16x3" if p3 else "wT16" if bf else "wT", layer, which)
+        return self._cached(("wT16x3" if p3 else "wT16" if bf else "wT", layer, which), lambda: ptr_array(
+            [(self.wT16x3 if p3 else self.wT16 if bf else self.wT)[layer, g, which].data_ptr() for g in (0, 1)]))
+
+    # ---- named pointer tables: parameter name of include/amid_hip.h -> value, bound by L.call_named.  Tables of parameters live on the
+    # engine, tables of a plan's tensors on the plan; each is built once (the buffers never move: engine_graph restores in place).
+    def _cached(self, key, build):
         c = self._ptr_cache.get(key)
         if c is None:
-            buf = self.wT16x3 if p3 else self.wT16 if bf else self.wT
-            c = ptr_array([buf[layer, g, which].data_ptr() for g in (0, 1)])
-            self._ptr_cache[key] = c
+            c = self._ptr_cache[key] = build()
         return c
+
+    def _fams(self):
+        """The twelve parameter families [layer][domain] of the one-launch encoder entry points."""
+        fp = self.dense
+        return self._cached("fams", lambda: {n: ptr_array([fp.ptr(f"sac{d}." + fmt.format(l=l)) for l in (0, 1) for d in (1, 2)])
+                                             for n, fmt in SASREC_FAMILIES})
+
+    def _lay(self):
+        """Per layer: the families as (domain 0, domain 1) pairs, what the strip and row-tile launches take."""
+        return self._cached("lay", lambda: [{n: self._pp("sac{d}." + fmt.format(l=l)) for n, fmt in SASREC_FAMILIES} for l in (0, 1)])
+
+    def _pos(self):
+        fp = self.dense
+        return self._cached("pos", lambda: dict(pos0=fp.ptr("sac1.pos_emb.weight"), pos1=fp.ptr("sac2.pos_emb.weight")))
+
+    def _scorer(self, names=("w1", "b1", "w2", "b2"), grad: bool = False):
+        """The scorer's four pointers (grad: their gradients') under `names`: the header spells them w1 .. b2, sw1 .. sb2 beside the
+        encoder's own w1 .. b2, dW1 .. db2."""
+        fp = self.dense
+        return self._cached(("scorer", names, grad), lambda: dict(zip(names, (
+            fp.ptr("predictModule.fc." + n, fp.grad if grad else None) for n in ("0.weight", "0.bias", "2.weight", "2.bias")))))
+
+    def _last_ln(self, names=("ln_w", "ln_b")):
+        """The last LayerNorm's (domain 0, domain 1) gains and biases under `names` (last_ln_w / last_ln_b in the head-on-forward entries)."""
+        return self._cached(("last_ln", names), lambda: dict(zip(names, (self._pp("sac{d}.last_layernorm.weight"),
+                                                                          self._pp("sac{d}.last_layernorm.bias")))))
+
+    def _wT_fams(self, bf16: bool):
+        """amid_sas_seq_bwd_f32's transposed-weight families [layer][domain]: the fp32 transposes or their one-plane bf16 images."""
+        buf = self.wT16 if bf16 else self.wT
+        return self._cached(("wT_fams", bool(bf16)), lambda: {
+            n: ptr_array([buf[l, g, j].data_ptr() for l in (0, 1) for g in (0, 1)]) for j, n in enumerate(("wqT", "wkT", "wvT", "woT", "w1T", "w2T"))})
+
+    def _wT_lists(self):
+        """(src, dst, n) of a step's 24 fp32 weight transposes: in_proj's q / k / v blocks, out_proj, conv1, conv2 of both layers and domains."""
+        def build():
+            fp, D, src, dst = self.dense, self.D, [], []
+            for l in (0, 1):
+                for g in (0, 1):
+                    pre = f"sac{g + 1}"
+                    src += [fp.ptr(f"{pre}.attention_layers.{l}.in_proj_weight", None, j * D * D) for j in range(3)]
+                    src += [fp.ptr(f"{pre}.attention_layers.{l}.out_proj.weight"), fp.ptr(f"{pre}.forward_layers.{l}.conv1.weight"),
+                            fp.ptr(f"{pre}.forward_layers.{l}.conv2.weight")]
+                    dst += [self.wT[l, g, w].data_ptr() for w in range(6)]
+            return ptr_array(src), ptr_array(dst), len(src)
+        return self._cached("wT_lists", build)
+
+    @staticmethod
+    def _seq_ptrs(pl: SasrecPlan):
+        """The plan's per-layer tensors as host pointer arrays: the layers' inputs and what the one-launch forward saves for the backward."""
+        if not hasattr(pl, "seq_ptrs"):
+            pa = lambda ts: ptr_array([t.data_ptr() for t in ts])          # noqa: E731
+            pl.seq_ptrs = dict(x_in=pa(pl.x[:2]), qn=pa(pl.qn), q=pa(pl.q), k=pa(pl.k), v=pa(pl.v), o=pa(pl.o), stats=pa(pl.stats), r=pa(pl.r),
+                               y=pa(pl.y), h=pa(pl.h))
+        return pl.seq_ptrs
+
+    @staticmethod
+    def _seq_grad_ptrs(pl: SasrecPlan):
+        """... and what the one-launch backward writes."""
+        if not hasattr(pl, "seq_grad_ptrs"):
+            pa = lambda ts: ptr_array([t.data_ptr() for t in ts])          # noqa: E731
+            pl.seq_grad_ptrs = dict(dpre2=pa(pl.dpre2), dpre1=pa(pl.dpre1), dr=pa(pl.dr), dq=pa(pl.dq_l), dk=pa(pl.dk_l), dv=pa(pl.dv_l),
+                                    ln1_part=pa(pl.ln1_part_s), ln2_part=pa(pl.ln2_part_s))
+        return pl.seq_grad_ptrs
 
     _bf16_bwd = False          # set per backward: the strip backward's products take bf16 images (compute = "bf16" on the strip path)
     _p3_bwd = False            # set per backward: ... three-plane images (compute = "fp32", products on bf16 pieces)
@@ -565,22 +639,14 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
     def _w16_images(self, planes: int):
         """(host pointer array of the 24 encoder weights [layer][domain][q, k, v, o, conv1, conv2], the image buffer) for `planes` bf16
         planes per weight (1: operands rounded to bf16; 3: hi + mid + lo = the fp32 weight exactly)."""
-        D, fp = self.D, self.dense
+        D = self.D
         # one buffer per plane count, never re-allocated: captured graphs hold these addresses, and a compute = "bf16" engine alternates between
         # three planes (its folded train step, round 6) and one (its evaluation forward)
         bufs = self.__dict__.setdefault("_w16_bufs", {})
         if planes not in bufs:
             bufs[planes] = torch.empty(2, 2, 6, planes, D * D, dtype=torch.bfloat16, device=self.device)
         self.w16 = bufs[planes]
-        if getattr(self, "_w16_src", None) is None:
-            srcs = []
-            for l in (0, 1):
-                for g in (1, 2):
-                    srcs += [fp.ptr(f"sac{g}.attention_layers.{l}.in_proj_weight", None, j * D * D) for j in range(3)]
-                    srcs += [fp.ptr(f"sac{g}.attention_layers.{l}.out_proj.weight"), fp.ptr(f"sac{g}.forward_layers.{l}.conv1.weight"),
-                             fp.ptr(f"sac{g}.forward_layers.{l}.conv2.weight")]
-            self._w16_src = ptr_array(srcs)
-        return self._w16_src, self.w16
+        return self._wT_lists()[0], self.w16
 
     def _p3_bwd_for(self, pl: SasrecPlan) -> bool:
         """Whether this plan's backward strips take their data-gradient products on bf16 pieces (three-plane images of the transposes)."""
@@ -707,17 +773,9 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
                 pl.w16_written = pl.wT16x3_written = True
             else:
                 self._enqueue_k1(pl, fp.ptr("sac1.pos_emb.weight"), fp.ptr("sac2.pos_emb.weight"), pl.tmq.data_ptr(), tr, SASREC_P_DROP, lf, gather_items)
-        def layer_ptrs(l):
-            pre = f"sac{{d}}"
-            return ((self._pp(f"{pre}.attention_layernorms.{l}.weight"), self._pp(f"{pre}.attention_layernorms.{l}.bias"),
-                     self._pp(f"{pre}.attention_layers.{l}.in_proj_weight"), self._pp(f"{pre}.attention_layers.{l}.in_proj_bias")),
-                    (self._pp(f"{pre}.attention_layers.{l}.out_proj.weight"), self._pp(f"{pre}.attention_layers.{l}.out_proj.bias"),
-                     self._pp(f"{pre}.forward_layernorms.{l}.weight"), self._pp(f"{pre}.forward_layernorms.{l}.bias"),
-                     self._pp(f"{pre}.forward_layers.{l}.conv1.weight"), self._pp(f"{pre}.forward_layers.{l}.conv1.bias"),
-                     self._pp(f"{pre}.forward_layers.{l}.conv2.weight"), self._pp(f"{pre}.forward_layers.{l}.conv2.bias")))
-
-        qkv0, rest0 = layer_ptrs(0)
-        qkv1, rest1 = layer_ptrs(1)
+        lay = self._lay()
+        qkv0, qkv1 = (tuple(lay[l][n] for n in QKV_FAMILIES) for l in (0, 1))
+        rest0, rest1 = (tuple(lay[l][n] for n in FFN_FAMILIES) for l in (0, 1))
 
         def attn_fwd(l):
             if live_fwd:
@@ -729,19 +787,10 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
 
         if pl.strip and self.SEQ_FORWARD and not self.inc_bs and L.value("amid_sas_seq_supported", B, T, D, self.H):
             # the whole encoder -- both layers, attention cores included -- as ONE launch, a workgroup per sequence (csrc/sasrec_seq.hip)
-            fam = lambda fmt: ptr_array([fp.ptr(fmt.format(d=d, l=l)) for l in (0, 1) for d in (1, 2)])      # noqa: E731  [layer][domain]
-            key = ("seq_fwd", pl.x[0].data_ptr())
-            c = self._ptr_cache.get(key)
-            if c is None:
-                tl = lambda ts: ptr_array([t.data_ptr() for t in ts])      # noqa: E731
-                c = (tl(pl.x[:2]), fam("sac{d}.attention_layernorms.{l}.weight"), fam("sac{d}.attention_layernorms.{l}.bias"),
-                     fam("sac{d}.attention_layers.{l}.in_proj_weight"), fam("sac{d}.attention_layers.{l}.in_proj_bias"),
-                     fam("sac{d}.attention_layers.{l}.out_proj.weight"), fam("sac{d}.attention_layers.{l}.out_proj.bias"),
-                     fam("sac{d}.forward_layernorms.{l}.weight"), fam("sac{d}.forward_layernorms.{l}.bias"),
-                     fam("sac{d}.forward_layers.{l}.conv1.weight"), fam("sac{d}.forward_layers.{l}.conv1.bias"),
-                     fam("sac{d}.forward_layers.{l}.conv2.weight"), fam("sac{d}.forward_layers.{l}.conv2.bias"),
-                     tl(pl.qn), tl(pl.q), tl(pl.k), tl(pl.v), tl(pl.o), tl(pl.stats), tl(pl.r), tl(pl.y), tl(pl.h))
-                self._ptr_cache[key] = c
+            sv, fams = self._seq_ptrs(pl), self._fams()
+            # what every form of it takes (the folded forms take ln_stat where the others take qn, and no y: sv's qn / y are then not bound)
+            enc = dict(n_layers=2, tmq=pl.tmq.data_ptr(), ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, H=self.H, live=lf, step_state=st, train=tr,
+                       p_drop=SASREC_P_DROP, stream=s)
             split = self._fwd_on_pieces(pl, B, T)
             if self._ceff() == "bf16" or split:       # this step's weights as bf16 fragment images (one plane: operands rounded to bf16;
                 planes = 3 if split else 1            # three: hi + mid + lo = the fp32 weight exactly), then the forward on them
@@ -751,40 +800,39 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
                 pl.w16_written = False
                 if split and getattr(pl, "tail2", False) and lf is not None:
                     # the folded step: qn / y are not stored -- row statistics instead (pl.ln_stat); the weight gradients rebuild them
-                    # (c: x, 12 parameter families, qn, q, k, v, o, stats, r, y, h)
-                    gather = (self.table.data_ptr(), pl.idx_all.data_ptr(), fp.ptr("sac1.pos_emb.weight"), fp.ptr("sac2.pos_emb.weight"))
+                    items = pl.xg.data_ptr() + 4 * 2 * shp.Mi * D
+                    gather = dict(self._pos(), table=self.table.data_ptr(), idx_all=pl.idx_all.data_ptr())      # (the gather forms' prologue)
                     if (self.HEAD_ON_FWD and getattr(self, "_fuse_head", False) and with_loss and not sum_loss and 16 < T <= 64
                             and self.hid <= 32 and NI <= 64):
                         # ... and a live sequence is a sample: its workgroup finishes with the sample's head (forward + loss + backward,
                         # what amid_head_fwd_bwd_own_vec_f32 does in enqueue_backward otherwise); the last layer's output is not stored
                         # (compute = "bf16" on the folded step: the same launch multiplying ONE piece per operand, BF16_FWD_ONE)
                         p1 = "_p1" if (gat and self._bf16_as_f32 and self.BF16_FWD_ONE) else ""
-                        L.call(f"amid_sas_seq_fwd_gather_head{p1}_f32" if gat else "amid_sas_seq_fwd_split_lnstat_head_f32", 2, c[0],
-                               pl.x[2].data_ptr() if self.HEAD_ON_FWD_KEEPS_X else None, *c[1:13], self._ln_stat(pl)[1], *c[14:20], c[21],
-                               pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, self.H, lf, st, tr, SASREC_P_DROP, w16.data_ptr(),
-                               self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"),
-                               pl.xg.data_ptr() + 4 * 2 * shp.Mi * D, fp.ptr("predictModule.fc.0.weight"), fp.ptr("predictModule.fc.0.bias"),
-                               fp.ptr("predictModule.fc.2.weight"), fp.ptr("predictModule.fc.2.bias"), pl.labels.data_ptr(),
-                               pl.domain.data_ptr(), NI, self.hid, pl.u.data_ptr(), pl.p1.data_ptr(), pl.p2.data_ptr(), pl.dp1.data_ptr(),
-                               pl.dp2.data_ptr(), pl.loss_part.data_ptr(), pl.dxbuf.data_ptr(), pl.dxg.data_ptr() + 4 * 2 * shp.Mi * D,
-                               pl.last_part.data_ptr(), self._hidg(pl).data_ptr(), *(gather if gat else ()), s)
+                        L.call_named(f"amid_sas_seq_fwd_gather_head{p1}_f32" if gat else "amid_sas_seq_fwd_split_lnstat_head_f32", sv, fams, enc,
+                                     gather, self._last_ln(("last_ln_w", "last_ln_b")), self._scorer(("sw1", "sb1", "sw2", "sb2")),
+                                     xout=pl.x[2].data_ptr() if self.HEAD_ON_FWD_KEEPS_X else None, ln_stat=self._ln_stat(pl)[1],
+                                     w16x3=w16.data_ptr(), items=items, labels=pl.labels.data_ptr(), domain_id=pl.domain.data_ptr(), NI=NI,
+                                     hid=self.hid, u=pl.u.data_ptr(), p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(), dp1=pl.dp1.data_ptr(),
+                                     dp2=pl.dp2.data_ptr(), loss_part=pl.loss_part.data_ptr(), dx=pl.dxbuf.data_ptr(),
+                                     ditems=pl.dxg.data_ptr() + 4 * 2 * shp.Mi * D, ln_part=pl.last_part.data_ptr(),
+                                     hidg=self._hidg(pl).data_ptr())
                         pl.head_done = True
                     elif gat:
                         p1 = "_p1" if (self._bf16_as_f32 and self.BF16_FWD_ONE) else ""
-                        L.call(f"amid_sas_seq_fwd_gather{p1}_f32", 2, c[0], pl.x[2].data_ptr(), *c[1:13], self._ln_stat(pl)[1], *c[14:20], c[21],
-                               pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, self.H, lf, st, tr, SASREC_P_DROP, w16.data_ptr(),
-                               pl.xg.data_ptr() + 4 * 2 * shp.Mi * D, NI, *gather, s)
+                        L.call_named(f"amid_sas_seq_fwd_gather{p1}_f32", sv, fams, enc, gather, xout=pl.x[2].data_ptr(),
+                                     ln_stat=self._ln_stat(pl)[1], w16x3=w16.data_ptr(), items=items, NI=NI)
                     else:
-                        L.call("amid_sas_seq_fwd_split_lnstat_f32", 2, c[0], pl.x[2].data_ptr(), *c[1:13], self._ln_stat(pl)[1], *c[14:20], c[21],
-                               pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, self.H, lf, st, tr, SASREC_P_DROP, w16.data_ptr(), s)
+                        L.call_named("amid_sas_seq_fwd_split_lnstat_f32", sv, fams, enc, xout=pl.x[2].data_ptr(), ln_stat=self._ln_stat(pl)[1],
+                                     w16x3=w16.data_ptr())
                     pl.lnstat_fwd = True
                 else:
                     pl.lnstat_fwd = False
-                    L.call("amid_sas_seq_fwd_split_f32" if split else "amid_sas_seq_fwd_bf16w_f32", 2, c[0], pl.x[2].data_ptr(), *c[1:],
-                           pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, self.H, lf, st, tr, SASREC_P_DROP, w16.data_ptr(), s)
+                    if split:
+                        L.call_named("amid_sas_seq_fwd_split_f32", sv, fams, enc, xout=pl.x[2].data_ptr(), w16x3=w16.data_ptr())
+                    else:
+                        L.call_named("amid_sas_seq_fwd_bf16w_f32", sv, fams, enc, xout=pl.x[2].data_ptr(), w16=w16.data_ptr())
             else:
-                L.call("amid_sas_seq_fwd_f32", 2, c[0], pl.x[2].data_ptr(), *c[1:], pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, self.H, lf, st, tr,
-                       SASREC_P_DROP, s)
+                L.call_named("amid_sas_seq_fwd_f32", sv, fams, enc, xout=pl.x[2].data_ptr())
         elif pl.strip:       # register-resident strip chains (csrc/sasrec_strip.hip): same operations, operands and saved tensors
             L.call("amid_sas_strip_qkv_fwd_f32", pl.x[0].data_ptr(), *qkv0, SASREC_LN_EPS, B, T, D, lf, pl.qn[0].data_ptr(), pl.q[0].data_ptr(),
                    pl.k[0].data_ptr(), pl.v[0].data_ptr(), s)
@@ -828,12 +876,11 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             return
         if getattr(self, "_fuse_head", False) and with_loss and not sum_loss:
             return                                   # train step: the head runs as ONE forward + backward launch in enqueue_backward
-        L.call("amid_head_fwd_f32", pl.x[2].data_ptr(), self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"), items,
-               fp.ptr("predictModule.fc.0.weight"), fp.ptr("predictModule.fc.0.bias"), fp.ptr("predictModule.fc.2.weight"),
-               fp.ptr("predictModule.fc.2.bias"), pl.labels.data_ptr() if with_loss else None, pl.domain.data_ptr() if with_loss else None,
-               B, T, NI, D, self.hid, SASREC_LN_EPS, pl.u.data_ptr(), pl.p1.data_ptr(), pl.p2.data_ptr(),
-               pl.dp1.data_ptr() if with_loss else None, pl.dp2.data_ptr() if with_loss else None,
-               pl.loss_part.data_ptr() if with_loss else None, s)
+        L.call_named("amid_head_fwd_f32", self._last_ln(), self._scorer(), x=pl.x[2].data_ptr(), items=items,
+                     labels=pl.labels.data_ptr() if with_loss else None, domain_id=pl.domain.data_ptr() if with_loss else None,
+                     B=B, T=T, NI=NI, D=D, hid=self.hid, eps=SASREC_LN_EPS, u=pl.u.data_ptr(), p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(),
+                     dp1=pl.dp1.data_ptr() if with_loss else None, dp2=pl.dp2.data_ptr() if with_loss else None,
+                     loss_part=pl.loss_part.data_ptr() if with_loss else None, stream=s)
         if with_loss and sum_loss:
             L.call("amid_sum_vector_f32", pl.loss_part.data_ptr(), B, pl.loss.data_ptr(), s)
 
@@ -976,6 +1023,14 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
                    pa(o[3].data_ptr() for o in outs), pl.loss_part.data_ptr(), pl.dr_loss_part.data_ptr() if self.dr else None,
                    pl.du.data_ptr(), ditems, pa(o[4].data_ptr() for o in outs), tr_src, tr_dst, n_tr, self.s)
 
+    def _head_io(self, pl: SasrecPlan, items: int, ditems: int):
+        """What the one-launch heads (forward + loss + backward) read and write beside the parameters, under the header's names."""
+        shp = pl.shape
+        return dict(x=pl.x[2].data_ptr(), items=items, labels=pl.labels.data_ptr(), domain_id=pl.domain.data_ptr(), B=shp.B, T=shp.Tenc, NI=shp.NI,
+                    D=self.D, hid=self.hid, eps=SASREC_LN_EPS, u=pl.u.data_ptr(), p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(), dp1=pl.dp1.data_ptr(),
+                    dp2=pl.dp2.data_ptr(), loss_part=pl.loss_part.data_ptr(), dx=pl.dxbuf.data_ptr(), ditems=ditems,
+                    ln_part=pl.last_part.data_ptr(), stream=self.s)
+
     def enqueue_backward(self, pl: SasrecPlan, train: bool) -> None:
         """Backward from pl.dp1 / pl.dp2 (dLoss/dp) to pl.uniq_grad (table rows) and dense.grad."""
         L, s, shp, D = lib(), self.s, pl.shape, self.D
@@ -983,17 +1038,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         st = self.step_state.data_ptr()
         tr = 1 if train else 0
         fp = self.dense
-        # transposed weights: in_proj q/k/v blocks, out_proj, conv1, conv2 for both layers and domains
-        src, dst = [], []
-        for l in (0, 1):
-            for g in (0, 1):
-                pre = f"sac{g + 1}"
-                for j in range(3):
-                    src.append(fp.ptr(f"{pre}.attention_layers.{l}.in_proj_weight", None, j * D * D))
-                src.append(fp.ptr(f"{pre}.attention_layers.{l}.out_proj.weight"))
-                src.append(fp.ptr(f"{pre}.forward_layers.{l}.conv1.weight"))
-                src.append(fp.ptr(f"{pre}.forward_layers.{l}.conv2.weight"))
-                dst += [self.wT[l, g, w].data_ptr() for w in range(6)]
+        tr_src, tr_dst, n_tr = self._wT_lists()      # transposed weights: in_proj q/k/v blocks, out_proj, conv1, conv2 for both layers and domains
         # compute = "bf16" on the strip path: the strip backward's data-gradient products take bf16 fragment images of the transposed weights
         # (the fp32 transposes are still refreshed: the row-tile fallbacks and tests read them)
         self._bf16_bwd = bool(self._ceff() == "bf16" and pl.strip)
@@ -1005,44 +1050,38 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         if self._bf16_bwd:
             if not hasattr(self, "wT16"):
                 self.wT16 = torch.empty(2, 2, 6, D * D, dtype=torch.bfloat16, device=self.device)
-            L.call("amid_sas_weights_bf16", ptr_array(src), len(src), D, 1, self.wT16.data_ptr(), s)
+            L.call("amid_sas_weights_bf16", tr_src, n_tr, D, 1, self.wT16.data_ptr(), s)
         if self._p3_bwd:
             if not getattr(pl, "wT16x3_written", False):           # (the train step's gather K1 wrote them with extra workgroups)
-                L.call("amid_sas_weights_bf16_planes", ptr_array(src), len(src), D, 1, 3, self._wT16x3_buf().data_ptr(), s)
+                L.call("amid_sas_weights_bf16_planes", tr_src, n_tr, D, 1, 3, self._wT16x3_buf().data_ptr(), s)
             pl.wT16x3_written = False
         items = pl.xg.data_ptr() + 4 * 2 * shp.Mi * D
         ditems = pl.dxg.data_ptr() + 4 * 2 * shp.Mi * D
         if (self.dr or self.itc_bs) and getattr(self, "_fuse_scorers", False):
-            self._enqueue_scorers_fused(pl, items, ditems, ptr_array(src), ptr_array(dst), len(src))
+            self._enqueue_scorers_fused(pl, items, ditems, tr_src, tr_dst, n_tr)
             self._enqueue_user_vectors_bwd(pl)
         elif self.dr:
-            L.call("amid_transpose_weights_f32", ptr_array(src), ptr_array(dst), len(src), D, s)
+            L.call("amid_transpose_weights_f32", tr_src, tr_dst, n_tr, D, s)
             self._enqueue_head_dr_bwd(pl, items, ditems)
         elif self.itc_bs:
-            L.call("amid_transpose_weights_f32", ptr_array(src), ptr_array(dst), len(src), D, s)
+            L.call("amid_transpose_weights_f32", tr_src, tr_dst, n_tr, D, s)
             self._enqueue_head_itc_bwd(pl, items, ditems)
         elif getattr(pl, "head_done", False):
             pl.head_done = False          # (the forward's workgroups ran the head: amid_sas_seq_fwd_split_lnstat_head_f32 in enqueue_forward)
         elif getattr(self, "_fuse_head", False) and getattr(pl, "tail2", False) and getattr(self, "_live_fwd", False) and self._live_list(pl) is not None:
             # the folded step: the scorer's weight gradients leave the head as per-sample hidden gradients (pl.hidg; the gradient tail sums
             # them, amid_grad_tail_live_f32) and the fp32 transposes are not refreshed (this step's strips read the three-plane images)
-            L.call("amid_head_fwd_bwd_own_vec_f32", pl.x[2].data_ptr(), self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"),
-                   items, fp.ptr("predictModule.fc.0.weight"), fp.ptr("predictModule.fc.0.bias"), fp.ptr("predictModule.fc.2.weight"),
-                   fp.ptr("predictModule.fc.2.bias"), pl.labels.data_ptr(), pl.domain.data_ptr(), B, T, NI, D, self.hid, SASREC_LN_EPS,
-                   pl.u.data_ptr(), pl.p1.data_ptr(), pl.p2.data_ptr(), pl.dp1.data_ptr(), pl.dp2.data_ptr(), pl.loss_part.data_ptr(),
-                   pl.dxbuf.data_ptr(), ditems, pl.last_part.data_ptr(), self._hidg(pl).data_ptr(), None, None, 0, s)
+            L.call_named("amid_head_fwd_bwd_own_vec_f32", self._last_ln(), self._scorer(), self._head_io(pl, items, ditems),
+                         hidg=self._hidg(pl).data_ptr(), tr_src=None, tr_dst=None, n_tr=0)
         elif getattr(self, "_fuse_head", False):
-            L.call("amid_head_fwd_bwd_own_f32" if getattr(self, "_live_fwd", False) and self._live_list(pl) is not None else "amid_head_fwd_bwd_f32", pl.x[2].data_ptr(), self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"),
-                   items, fp.ptr("predictModule.fc.0.weight"), fp.ptr("predictModule.fc.0.bias"), fp.ptr("predictModule.fc.2.weight"),
-                   fp.ptr("predictModule.fc.2.bias"), pl.labels.data_ptr(), pl.domain.data_ptr(), B, T, NI, D, self.hid, SASREC_LN_EPS,
-                   pl.u.data_ptr(), pl.p1.data_ptr(), pl.p2.data_ptr(), pl.dp1.data_ptr(), pl.dp2.data_ptr(), pl.loss_part.data_ptr(),
-                   pl.dxbuf.data_ptr(), ditems, pl.last_part.data_ptr(), pl.sc_part.data_ptr(), ptr_array(src), ptr_array(dst), len(src), s)
+            L.call_named("amid_head_fwd_bwd_own_f32" if getattr(self, "_live_fwd", False) and self._live_list(pl) is not None else "amid_head_fwd_bwd_f32",
+                         self._last_ln(), self._scorer(), self._head_io(pl, items, ditems), sc_part=pl.sc_part.data_ptr(), tr_src=tr_src,
+                         tr_dst=tr_dst, n_tr=n_tr)
         else:
-            L.call("amid_head_bwd_f32", pl.x[2].data_ptr(), self._pp("sac{d}.last_layernorm.weight"), pl.u.data_ptr(), items,
-                   fp.ptr("predictModule.fc.0.weight"), fp.ptr("predictModule.fc.0.bias"), fp.ptr("predictModule.fc.2.weight"),
-                   fp.ptr("predictModule.fc.2.bias"), pl.p1.data_ptr(), pl.p2.data_ptr(), pl.dp1.data_ptr(), pl.dp2.data_ptr(), B, T, NI, D,
-                   self.hid, SASREC_LN_EPS, pl.dxbuf.data_ptr(), ditems, pl.last_part.data_ptr(), pl.sc_part.data_ptr(),
-                   ptr_array(src), ptr_array(dst), len(src), s)
+            L.call_named("amid_head_bwd_f32", self._last_ln(), self._scorer(), x=pl.x[2].data_ptr(), u=pl.u.data_ptr(), items=items,
+                         p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(), dp1=pl.dp1.data_ptr(), dp2=pl.dp2.data_ptr(), B=B, T=T, NI=NI, D=D,
+                         hid=self.hid, eps=SASREC_LN_EPS, dx=pl.dxbuf.data_ptr(), ditems=ditems, ln_part=pl.last_part.data_ptr(),
+                         sc_part=pl.sc_part.data_ptr(), tr_src=tr_src, tr_dst=tr_dst, n_tr=n_tr, stream=s)
         def ffn_bwd_args(l):
             return (pl.tmq.data_ptr(), pl.h[l].data_ptr(), pl.r[l].data_ptr(), self._pp(f"sac{{d}}.forward_layernorms.{l}.weight"),
                     self._wT(l, 4), self._wT(l, 5), self._wT(l, 3))
@@ -1070,22 +1109,10 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         pl.seq_bwd_used = seq              # (what THIS backward ran: _seq_backward() depends on the step being enqueued; bench.py and tests read this)
         if seq:
             # the five launches below as one workgroup-long chain per live sequence
-            pa = lambda ts: ptr_array([t.data_ptr() for t in ts])          # noqa: E731
-            key = ("seq_bwd", id(pl), bf)
-            c = self._ptr_cache.get(key)
-            if c is None:
-                def wts(which):
-                    return ptr_array([(self.wT16 if bf else self.wT)[l, g, which].data_ptr() for l in (0, 1) for g in (0, 1)])
-                def lnw(fmt):
-                    return ptr_array([fp.ptr(fmt.format(d=g + 1, l=l)) for l in (0, 1) for g in (0, 1)])
-                c = dict(h=pa(pl.h), r=pa(pl.r), x=pa(pl.x[:2]), q=pa(pl.q), k=pa(pl.k), v=pa(pl.v), o=pa(pl.o), stats=pa(pl.stats),
-                         ln1=lnw("sac{d}.attention_layernorms.{l}.weight"), ln2=lnw("sac{d}.forward_layernorms.{l}.weight"),
-                         wq=wts(0), wk=wts(1), wv=wts(2), wo=wts(3), w1=wts(4), w2=wts(5), dpre2=pa(pl.dpre2), dpre1=pa(pl.dpre1),
-                         dr=pa(pl.dr), dq=pa(pl.dq_l), dk=pa(pl.dk_l), dv=pa(pl.dv_l), ln1p=pa(pl.ln1_part_s), ln2p=pa(pl.ln2_part_s))
-                self._ptr_cache[key] = c
-            L.call("amid_sas_seq_bwd_f32", 2, pl.dxbuf.data_ptr(), tm, c["h"], c["r"], c["x"], c["q"], c["k"], c["v"], c["o"], c["stats"],
-                   c["ln1"], c["ln2"], c["wq"], c["wk"], c["wv"], c["wo"], c["w1"], c["w2"], SASREC_LN_EPS, B, T, D, self.H, lv, st, tr,
-                   SASREC_P_DROP, c["dpre2"], c["dpre1"], c["dr"], pl.d_o.data_ptr(), c["dq"], c["dk"], c["dv"], dx_in, c["ln1p"], c["ln2p"], bf, s)
+            sv = self._seq_ptrs(pl)
+            L.call_named("amid_sas_seq_bwd_f32", sv, self._seq_grad_ptrs(pl), self._fams(), self._wT_fams(bf), n_layers=2, dxo=pl.dxbuf.data_ptr(),
+                         tmq=tm, x=sv["x_in"], ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, H=self.H, live=lv, step_state=st, train=tr,
+                         p_drop=SASREC_P_DROP, d_o=pl.d_o.data_ptr(), dx=dx_in, mma_bf16=bf, stream=s)
         elif pl.strip:
             ln1p, ln2p = pl.ln1_part, pl.ln2_part
             # a train step's index sort rides in these three launches (phases 2, 3, 4; phase 1 rode in the catch-up launch)
@@ -1100,13 +1127,14 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             attn_bwd(1)
             # layer 1's q / k / v + LayerNorm1 backward and layer 0's feed-forward / out-projection backward: one launch
             if t2:      # ... whose idle CUs also sum the scorer's weight gradients from the head's per-sample hidden gradients
-                G = fp.grad
-                L.call("amid_sas_strip_qkv_bwd_sort_scorer_f32", pl.dq_l[1].data_ptr(), pl.dk_l[1].data_ptr(), pl.dv_l[1].data_ptr(), pl.dr[1].data_ptr(),
-                       pl.x[1].data_ptr(), self._pp("sac{d}.attention_layernorms.1.weight"), self._wT(1, 0), self._wT(1, 1), self._wT(1, 2),
-                       SASREC_LN_EPS, B, T, D, lv, ln1p[1].data_ptr(), tm, h0, r0, lnw0, w1T0, w2T0, woT0, 0, st, tr, SASREC_P_DROP,
-                       pl.dpre2[0].data_ptr(), pl.dpre1[0].data_ptr(), pl.dr[0].data_ptr(), pl.d_o.data_ptr(), ln2p[0].data_ptr(), plan_addr, 3, bf,
-                       self._hidg(pl).data_ptr(), pl.u.data_ptr(), items, NI, self.hid, fp.ptr("predictModule.fc.0.weight", G),
-                       fp.ptr("predictModule.fc.0.bias", G), fp.ptr("predictModule.fc.2.weight", G), fp.ptr("predictModule.fc.2.bias", G), s)
+                L.call_named("amid_sas_strip_qkv_bwd_sort_scorer_f32", self._scorer(("dW1", "db1", "dW2", "db2"), grad=True),
+                             dq=pl.dq_l[1].data_ptr(), dk=pl.dk_l[1].data_ptr(), dv=pl.dv_l[1].data_ptr(), dr=pl.dr[1].data_ptr(),
+                             x=pl.x[1].data_ptr(), ln_w=self._pp("sac{d}.attention_layernorms.1.weight"), wqT=self._wT(1, 0), wkT=self._wT(1, 1),
+                             wvT=self._wT(1, 2), ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, live=lv, ln_part=ln1p[1].data_ptr(), tmq=tm, fh=h0, fr=r0,
+                             fln_w=lnw0, fw1T=w1T0, fw2T=w2T0, fwoT=woT0, flayer=0, step_state=st, train=tr, p_drop=SASREC_P_DROP,
+                             fdpre2=pl.dpre2[0].data_ptr(), fdpre1=pl.dpre1[0].data_ptr(), fdr=pl.dr[0].data_ptr(), fd_o=pl.d_o.data_ptr(),
+                             fln_part=ln2p[0].data_ptr(), sort_plan=plan_addr, sort_phase=3, mma_bf16=bf, hidg=self._hidg(pl).data_ptr(),
+                             u=pl.u.data_ptr(), items=items, NI=NI, hid=self.hid, stream=s)
             else:
                 L.call(f"amid_sas_strip_qkv_bwd{sfx}_f32", pl.dq_l[1].data_ptr(), pl.dk_l[1].data_ptr(), pl.dv_l[1].data_ptr(), pl.dr[1].data_ptr(),
                        pl.x[1].data_ptr(), self._pp("sac{d}.attention_layernorms.1.weight"), self._wT(1, 0), self._wT(1, 1), self._wT(1, 2),
@@ -1151,17 +1179,16 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             if getattr(pl, "lnstat_fwd", False):      # the forward stored row statistics instead of qn / y: the operands of q's and conv1's
                 for l in (0, 1):                       # gradients are rebuilt from x / r while they are staged
                     xx[6 * l + 0], xx[6 * l + 4] = pl.x[l].data_ptr(), pl.r[l].data_ptr()
-                fam = lambda fmt: ptr_array([fp.ptr(fmt.format(d=d, l=l)) for l in (0, 1) for d in (1, 2)])      # noqa: E731  [layer][domain]
                 self._wgrad_one = True              # (the folded bf16 step: this launch on ONE piece per operand, _wgrad_mode -> 4)
                 try:
                     wmode = self._wgrad_mode(D)
                 finally:
                     self._wgrad_one = False
-                L.call("amid_sas_wgrad_rows_sort_ln_f32", ptr_array(dy), ptr_array(xx), 2, M, D, pl.splits,
-                       ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]), ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]),
-                       self._own_rows(pl), B, T, wmode, self._sort_plan_c(pl), self._ln_stat(pl)[1],
-                       fam("sac{d}.attention_layernorms.{l}.weight"), fam("sac{d}.attention_layernorms.{l}.bias"),
-                       fam("sac{d}.forward_layernorms.{l}.weight"), fam("sac{d}.forward_layernorms.{l}.bias"), s)
+                # (of the families it takes the four LayerNorm ones)
+                L.call_named("amid_sas_wgrad_rows_sort_ln_f32", self._fams(), dy=ptr_array(dy), x=ptr_array(xx), n_layers=2, M=M, D=D,
+                             splits=pl.splits, w_part=ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]),
+                             b_part=ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]), row_domain=self._own_rows(pl), B=B, T=T,
+                             mma_bf16=wmode, sort_plan=self._sort_plan_c(pl), ln_stat=self._ln_stat(pl)[1], stream=s)
             else:
                 L.call("amid_sas_wgrad_rows_sort_f32", ptr_array(dy), ptr_array(xx), 2, M, D, pl.splits,
                        ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]), ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]),
@@ -1471,31 +1498,30 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         else:
             self._enqueue_eval_encoders(pl, build_images)
         ids = pl.idx_all.data_ptr() + 4 * 2 * shp.Mi
-        outs = (pl.ev_u.data_ptr() if want_scores else None, pl.ev_p.data_ptr() if want_scores else None, pl.ev_rank.data_ptr(),
-                pl.ev_rank_raw.data_ptr(), pl.ev_loss_part.data_ptr() if with_loss else None, s)
+        head = dict(table=self.table.data_ptr(), ids=ids, labels=pl.labels.data_ptr() if with_loss else None, domain_id=pl.domain.data_ptr(),
+                    B=B, NI=NI, D=D, hid=self.hid, fix_value=float(fix_value), u=pl.ev_u.data_ptr() if want_scores else None,
+                    p=pl.ev_p.data_ptr() if want_scores else None, rank=pl.ev_rank.data_ptr(), rank_raw=pl.ev_rank_raw.data_ptr(),
+                    loss_part=pl.ev_loss_part.data_ptr() if with_loss else None, stream=s)
         if self.dr or self.itc_bs:       # the user vectors by this model's own launches (pl.u [2, B, D]), read by the head
             # isItC at the batch sizes amid_itc_mix_fwd_f32 runs its 512-thread form on: the mix is the head's prologue, from pl.u_raw
             fold = bool(self.itc_bs and 32 <= B <= 256 and D in (64, 128))
             self._enqueue_user_vectors(pl, mix=not fold)
-            mixargs = (None,) * 5 + (0.0, None)
+            mix = dict(itc_s=None, w_nn=None, b_nn=None, w_bs=None, b_bs=None, threshold=0.0, gate=None)
             if fold:
-                mixargs = (pl.itc_s.data_ptr(), self._pp("itc_d{d}.trans_nn.weight"), self._pp("itc_d{d}.trans_nn.bias"),
-                           self._pp("itc_d{d}.trans_bs.weight"), self._pp("itc_d{d}.trans_bs.bias"), self.itc_threshold, pl.itc_gate.data_ptr())
-            L.call("amid_eval_head_u_f32", (pl.u_raw if fold else pl.u).data_ptr(), B * D, self.table.data_ptr(), ids, *self._scorer_ptrs(),
-                   pl.labels.data_ptr() if with_loss else None, pl.domain.data_ptr(), B, NI, D, self.hid, float(fix_value), *outs[:-1],
-                   *mixargs, s)
+                mix = dict(itc_s=pl.itc_s.data_ptr(), w_nn=self._pp("itc_d{d}.trans_nn.weight"), b_nn=self._pp("itc_d{d}.trans_nn.bias"),
+                           w_bs=self._pp("itc_d{d}.trans_bs.weight"), b_bs=self._pp("itc_d{d}.trans_bs.bias"), threshold=self.itc_threshold,
+                           gate=pl.itc_gate.data_ptr())
+            L.call_named("amid_eval_head_u_f32", self._scorer(), head, mix, u_src=(pl.u_raw if fold else pl.u).data_ptr(), u_dom_stride=B * D)
             return
-        ln_w, ln_b, ln_eps = self._eval_last_ln()
-        L.call("amid_eval_head_f32", pl.x[2].data_ptr(), ln_w, ln_b, self.table.data_ptr(), ids, *self._scorer_ptrs(),
-               pl.labels.data_ptr() if with_loss else None, pl.domain.data_ptr(), B, T, NI, D, self.hid, ln_eps, float(fix_value), *outs)
+        L.call_named("amid_eval_head_f32", self._eval_last_ln(), self._scorer(), head, x=pl.x[2].data_ptr(), T=T)
 
     def _eval_through_forward(self) -> bool:
         """Whether the evaluation batch's encoders are enqueue_forward's own launches (isInC: the token group in front of them)."""
         return bool(self.inc_bs)
 
     def _eval_last_ln(self):
-        """(gain pointers, bias pointers, eps) of the LayerNorm amid_eval_head_f32 applies in front of the mean over time (null pointers: none)."""
-        return self._pp("sac{d}.last_layernorm.weight"), self._pp("sac{d}.last_layernorm.bias"), SASREC_LN_EPS
+        """ln_w, ln_b, eps of the LayerNorm amid_eval_head_f32 applies in front of the mean over time (null pointers: none)."""
+        return dict(self._last_ln(), eps=SASREC_LN_EPS)
 
     def _enqueue_eval_images(self, pl: SasrecPlan) -> None:
         """The weight images the evaluation's forward reads, built once per evaluation (eval_epoch: the batches' launches only read them)."""
@@ -1511,7 +1537,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         B, T = shp.B, shp.Tenc
         fp, st = self.dense, self.step_state.data_ptr()
         lf = None if self.itc_bs else pl.live.data_ptr()      # isItC: the pair-max reads both domains' rows of every sample
-        pos = (fp.ptr("sac1.pos_emb.weight"), fp.ptr("sac2.pos_emb.weight"))
+        pos = self._pos()
         if not L.value("amid_sas_seq_supported", B, T, D, self.H):       # eval_fused_ok said yes: the long shape (_eval_long)
             self._enqueue_eval_encoders_long(pl, lf, pos)
             return
@@ -1525,64 +1551,52 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
                 L.call("amid_sas_weights_bf16_planes", src, 24, D, 0, 3, w16.data_ptr(), s)
         elif split and build_images:          # the gather's extra workgroups write the weights' three-plane images (the forward's operands)
             src, w16 = self._w16_images(3)
-            L.call("amid_embed_fwd_w16_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), *pos, B, T, D, 0, pl.xg.data_ptr(), pl.tmq.data_ptr(),
+            L.call("amid_embed_fwd_w16_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos["pos0"], pos["pos1"], B, T, D, 0, pl.xg.data_ptr(), pl.tmq.data_ptr(),
                    st, 0, SASREC_P_DROP, lf, None, None, src, 24, 3, w16.data_ptr(), None, s)
         else:
             if split:
                 src, w16 = self._w16_images(3)
             if lf is not None:
-                L.call("amid_embed_fwd_live_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), *pos, B, T, D, 0, pl.xg.data_ptr(),
+                L.call("amid_embed_fwd_live_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos["pos0"], pos["pos1"], B, T, D, 0, pl.xg.data_ptr(),
                        pl.tmq.data_ptr(), st, 0, SASREC_P_DROP, lf, s)
             else:
-                L.call("amid_embed_fwd_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), *pos, B, T, D, 0, pl.xg.data_ptr(), pl.tmq.data_ptr(),
+                L.call("amid_embed_fwd_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos["pos0"], pos["pos1"], B, T, D, 0, pl.xg.data_ptr(), pl.tmq.data_ptr(),
                        st, 0, SASREC_P_DROP, s)
-        fam = lambda fmt: ptr_array([fp.ptr(fmt.format(d=d, l=l)) for l in (0, 1) for d in (1, 2)])      # noqa: E731  [layer][domain]
-        key = ("eval_fwd", id(pl))
-        c = self._ptr_cache.get(key)
-        if c is None:
-            c = (fam("sac{d}.attention_layernorms.{l}.weight"), fam("sac{d}.attention_layernorms.{l}.bias"),
-                 fam("sac{d}.attention_layers.{l}.in_proj_weight"), fam("sac{d}.attention_layers.{l}.in_proj_bias"),
-                 fam("sac{d}.attention_layers.{l}.out_proj.weight"), fam("sac{d}.attention_layers.{l}.out_proj.bias"),
-                 fam("sac{d}.forward_layernorms.{l}.weight"), fam("sac{d}.forward_layernorms.{l}.bias"),
-                 fam("sac{d}.forward_layers.{l}.conv1.weight"), fam("sac{d}.forward_layers.{l}.conv1.bias"),
-                 fam("sac{d}.forward_layers.{l}.conv2.weight"), fam("sac{d}.forward_layers.{l}.conv2.bias"))
-            self._ptr_cache[key] = c
+        fams = self._fams()
+        enc = dict(n_layers=2, xout=pl.x[2].data_ptr(), ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, H=self.H, live=lf, stream=s)
         if gat:
-            L.call("amid_sas_seq_fwd_gather_infer_f32", 2, pl.x[2].data_ptr(), *c, SASREC_LN_EPS, B, T, D, self.H, lf, w16.data_ptr(),
-                   self.table.data_ptr(), pl.idx_all.data_ptr(), *pos, s)
+            L.call_named("amid_sas_seq_fwd_gather_infer_f32", fams, enc, pos, w16x3=w16.data_ptr(), table=self.table.data_ptr(),
+                         idx_all=pl.idx_all.data_ptr())
         elif split:
-            L.call("amid_sas_seq_fwd_split_infer_f32", 2, pl.x[0].data_ptr(), pl.x[2].data_ptr(), *c, pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D,
-                   self.H, lf, w16.data_ptr(), s)
+            L.call_named("amid_sas_seq_fwd_split_infer_f32", fams, enc, x0=pl.x[0].data_ptr(), tmq=pl.tmq.data_ptr(), w16x3=w16.data_ptr())
         else:              # D 64 / compute = "bf16" / FWD_SPLIT off: the saving forward over the live sequences
-            tl = lambda ts: ptr_array([t.data_ptr() for t in ts])      # noqa: E731
-            saved = (tl(pl.qn), tl(pl.q), tl(pl.k), tl(pl.v), tl(pl.o), tl(pl.stats), tl(pl.r), tl(pl.y), tl(pl.h))
+            sv = self._seq_ptrs(pl)
             if self.compute == "bf16":
                 src, w16 = self._w16_images(1)
                 L.call("amid_sas_weights_bf16_planes", src, 24, D, 0, 1, w16.data_ptr(), s)
-                L.call("amid_sas_seq_fwd_bf16w_f32", 2, tl(pl.x[:2]), pl.x[2].data_ptr(), *c, *saved, pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D,
-                       self.H, lf, st, 0, SASREC_P_DROP, w16.data_ptr(), s)
+                L.call_named("amid_sas_seq_fwd_bf16w_f32", fams, enc, sv, tmq=pl.tmq.data_ptr(), step_state=st, train=0, p_drop=SASREC_P_DROP,
+                             w16=w16.data_ptr())
             else:
-                L.call("amid_sas_seq_fwd_f32", 2, tl(pl.x[:2]), pl.x[2].data_ptr(), *c, *saved, pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, self.H,
-                       lf, st, 0, SASREC_P_DROP, s)
+                L.call_named("amid_sas_seq_fwd_f32", fams, enc, sv, tmq=pl.tmq.data_ptr(), step_state=st, train=0, p_drop=SASREC_P_DROP)
 
     def _enqueue_eval_encoders_long(self, pl: SasrecPlan, lf, pos) -> None:
         """64 < T <= 256: six launches up to pl.x[2], in the plan's q / k / v / o buffers; no gathered rows, nothing saved for a backward."""
         L, s, shp, D = lib(), self.s, pl.shape, self.D
-        B, T = shp.B, shp.Tenc
-        pre = "sac{d}"
-        lay = lambda l, names: tuple(self._pp(f"{pre}.{n}".replace("#", str(l))) for n in names)      # noqa: E731
-        qkv_n = ("attention_layernorms.#.weight", "attention_layernorms.#.bias", "attention_layers.#.in_proj_weight", "attention_layers.#.in_proj_bias")
-        rest_n = ("attention_layers.#.out_proj.weight", "attention_layers.#.out_proj.bias", "forward_layernorms.#.weight", "forward_layernorms.#.bias",
-                  "forward_layers.#.conv1.weight", "forward_layers.#.conv1.bias", "forward_layers.#.conv2.weight", "forward_layers.#.conv2.bias")
-        out = lambda l: (pl.qn[l].data_ptr(), pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr())      # noqa: E731
-        L.call("amid_sas_strip_qkv_fwd_gather_infer_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), *pos, *lay(0, qkv_n), SASREC_LN_EPS, B, T, D,
-               lf, pl.tmq.data_ptr(), *out(0), s)
+        lay = self._lay()
+        dims = dict(B=shp.B, T=shp.Tenc, D=D, live=lf, stream=s)
+        out = lambda l, pre="": {pre + n: getattr(pl, n)[l].data_ptr() for n in ("qn", "q", "k", "v")}      # noqa: E731
+        # (a layer's table under its q / k / v launch's names; under the next layer's, n..., in the launch in front of it)
+        qkv = lambda l, pre="": dict(out(l, pre), **{pre + "ln_w": lay[l]["ln1_w"], pre + "ln_b": lay[l]["ln1_b"],      # noqa: E731
+                                                     pre + "w_in": lay[l]["w_in"], pre + "b_in": lay[l]["b_in"]})
+        L.call_named("amid_sas_strip_qkv_fwd_gather_infer_f32", pos, qkv(0), dims, table=self.table.data_ptr(), idx_all=pl.idx_all.data_ptr(),
+                     ln_eps=SASREC_LN_EPS, tmq=pl.tmq.data_ptr())
         for l in (0, 1):
-            L.call("amid_attn_fwd_long_live_infer_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), B, T, D, self.H,
-                   pl.o[l].data_ptr(), lf, s)
-            nxt = (*lay(1, qkv_n), *out(1)) if l == 0 else (None,) * 8
-            L.call("amid_sas_strip_oproj_ffn_fwd_infer_f32", pl.o[l].data_ptr(), pl.qn[l].data_ptr(), *lay(l, rest_n), pl.tmq.data_ptr(),
-                   SASREC_LN_EPS, B, T, D, lf, None if l == 0 else pl.x[2].data_ptr(), *nxt, s)
+            L.call_named("amid_attn_fwd_long_live_infer_f32", dims, q=pl.q[l].data_ptr(), k=pl.k[l].data_ptr(), v=pl.v[l].data_ptr(), H=self.H,
+                         o=pl.o[l].data_ptr())
+            nxt = qkv(1, "n") if l == 0 else dict.fromkeys(qkv(1, "n"))
+            L.call_named("amid_sas_strip_oproj_ffn_fwd_infer_f32", lay[l], nxt, dims, o=pl.o[l].data_ptr(), qn=pl.qn[l].data_ptr(),
+                         ln_w=lay[l]["ln2_w"], ln_b=lay[l]["ln2_b"], tmq=pl.tmq.data_ptr(), ln_eps=SASREC_LN_EPS,
+                         xo=None if l == 0 else pl.x[2].data_ptr())
 
     def capture_eval(self, pl: SasrecPlan, fix_value: float, with_loss: bool = True) -> None:
         """The evaluation batch as a hipGraph over the plan's static inputs (parameters are read at replay time and the forward's weight
@@ -1653,11 +1667,6 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
             self._fr_ws = ws
         return ws
 
-    def _scorer_ptrs(self):
-        fp = self.dense
-        return (fp.ptr("predictModule.fc.0.weight"), fp.ptr("predictModule.fc.0.bias"), fp.ptr("predictModule.fc.2.weight"),
-                fp.ptr("predictModule.fc.2.bias"))
-
     def enqueue_full_rank(self, pl: SasrecPlan, pos: torch.Tensor, domain: torch.Tensor, pools, own: Optional[torch.Tensor],
                           own_off: Optional[torch.Tensor], rows: Optional[torch.Tensor], fix_value: float, rank: torch.Tensor,
                           rank_raw: torch.Tensor, scores: Optional[torch.Tensor] = None) -> None:
@@ -1671,7 +1680,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         ws = self._full_rank_workspace(B, p1.numel(), p2.numel(), 0)
         ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
         lib().call("amid_full_rank_f32", u.data_ptr(), stride, pos.data_ptr(), domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(),
-                   p2.numel(), ptr(own), ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer_ptrs(), self.D, self.hid,
+                   p2.numel(), ptr(own), ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer().values(), self.D, self.hid,
                    float(fix_value), ws.data_ptr(), pl.err.data_ptr(), rank.data_ptr(), rank_raw.data_ptr(), ptr(scores),
                    0 if scores is None else scores.shape[1], self.s)
 
@@ -1685,7 +1694,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
         ws = self._full_rank_workspace(B, p1.numel(), p2.numel(), int(k))
         ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
         lib().call("amid_topk_f32", u.data_ptr(), stride, domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel(), ptr(own),
-                   ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer_ptrs(), self.D, self.hid, int(k),
+                   ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer().values(), self.D, self.hid, int(k),
                    1 if exclude_history else 0, ws.data_ptr(), pl.err.data_ptr(), ids.data_ptr(), scores.data_ptr(), self.s)
 
     # ------------------------------------------------------------------ parameter interchange

@@ -228,11 +228,11 @@ class Bert4recEngine(SasrecEngine):
             return
         if getattr(self, "_fuse_head", False) and with_loss and not sum_loss:
             return                                   # train step: the head runs as ONE forward + backward launch in enqueue_backward
-        L.call("amid_head_fwd_f32", pl.x[2].data_ptr(), None, None, items, fp.ptr("predictModule.fc.0.weight"), fp.ptr("predictModule.fc.0.bias"),
-               fp.ptr("predictModule.fc.2.weight"), fp.ptr("predictModule.fc.2.bias"), pl.labels.data_ptr() if with_loss else None,
-               pl.domain.data_ptr() if with_loss else None, B, T, NI, D, self.hid, 0.0, pl.u.data_ptr(), pl.p1.data_ptr(), pl.p2.data_ptr(),
-               pl.dp1.data_ptr() if with_loss else None, pl.dp2.data_ptr() if with_loss else None,
-               pl.loss_part.data_ptr() if with_loss else None, s)
+        L.call_named("amid_head_fwd_f32", self._scorer(), x=pl.x[2].data_ptr(), ln_w=None, ln_b=None, items=items,
+                     labels=pl.labels.data_ptr() if with_loss else None, domain_id=pl.domain.data_ptr() if with_loss else None, B=B, T=T, NI=NI,
+                     D=D, hid=self.hid, eps=0.0, u=pl.u.data_ptr(), p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(),
+                     dp1=pl.dp1.data_ptr() if with_loss else None, dp2=pl.dp2.data_ptr() if with_loss else None,
+                     loss_part=pl.loss_part.data_ptr() if with_loss else None, stream=s)
         if with_loss and sum_loss:
             L.call("amid_sum_vector_f32", pl.loss_part.data_ptr(), B, pl.loss.data_ptr(), s)
 
@@ -357,11 +357,12 @@ class Bert4recEngine(SasrecEngine):
         sfx = "_p3_f32" if p3 else "_f32"
         trl = self._transpose_lists() if pl.need_grad and not p3 else None
         pl.transposed_in_forward = trl is not None or p3
-        n_tr = len(trl[2]) if trl else 0
+        tr_src, tr_dst, tr_rows, tr_cols = trl or (None,) * 4
+        n_tr = len(tr_rows) if trl else 0
         sv = (lambda t: t.data_ptr()) if save else (lambda t: None)
         L.call("amid_bert_strip_qkv_fwd_pro" + sfx, pl.x[0].data_ptr(), p0["la1"], p0["lb1"], i0["w3"] if p3 else p0["w3"], p0["b3"], B, T, lf, sv(pl.y[0]),
                pl.q[0].data_ptr(), pl.k[0].data_ptr(), pl.v[0].data_ptr(), None if self.comp else pl.in_seq_d2.data_ptr(), B * T,
-               pl.key_keep.data_ptr(), trl[0] if trl else None, trl[1] if trl else None, trl[2] if trl else None, trl[3] if trl else None, n_tr, s)
+               pl.key_keep.data_ptr(), tr_src, tr_dst, tr_rows, tr_cols, n_tr, s)
         for l, p in ((0, p0), (1, p1)):
             if live_attn:
                 L.call("amid_attn_bert_fwd_live_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.key_keep.data_ptr(), B, T, D,
@@ -401,7 +402,7 @@ class Bert4recEngine(SasrecEngine):
         return False
 
     def _eval_last_ln(self):
-        return None, None, 0.0
+        return dict(ln_w=None, ln_b=None, eps=0.0)
 
     def _enqueue_eval_images(self, pl) -> None:
         if self._p3(pl):
@@ -413,18 +414,18 @@ class Bert4recEngine(SasrecEngine):
                     and lib().value("amid_bert_seq_infer_supported", shp.B, shp.Tenc, self.D, self.H))
 
     def _seq_infer_ptrs(self):
-        """The one-launch encoder's pointer arrays: [block][domain] families (w3 / b3: [block][q, k, v][domain]), weights as tile images."""
+        """The one-launch encoder's pointer arrays under the header's names: [block][domain] families (w3 / b3: [block][q, k, v][domain]), weights as tile images."""
         c = self._ptr_cache.get("bert_seq_infer")
         if c is None:
             fp, I = self.dense, self._img
             fam = lambda fmt: ptr_array([fp.ptr(fmt.format(d=d, l=l)) for l in (0, 1) for d in (1, 2)])      # noqa: E731
             img = lambda i: ptr_array([I(l, g, i) for l in (0, 1) for g in (0, 1)])                          # noqa: E731
-            c = (fam("transform{d}.{l}.input_sublayer.norm.a_2"), fam("transform{d}.{l}.input_sublayer.norm.b_2"),
-                 ptr_array([I(l, g, j) for l in (0, 1) for j in range(3) for g in (0, 1)]),
-                 ptr_array([fp.ptr(f"transform{d}.{l}.attention.linear_layers.{j}.bias") for l in (0, 1) for j in range(3) for d in (1, 2)]),
-                 img(3), fam("transform{d}.{l}.attention.output_linear.bias"),
-                 fam("transform{d}.{l}.output_sublayer.norm.a_2"), fam("transform{d}.{l}.output_sublayer.norm.b_2"),
-                 img(4), fam("transform{d}.{l}.feed_forward.w_1.bias"), img(8), fam("transform{d}.{l}.feed_forward.w_2.bias"))
+            c = dict(la1=fam("transform{d}.{l}.input_sublayer.norm.a_2"), lb1=fam("transform{d}.{l}.input_sublayer.norm.b_2"),
+                     w3_img=ptr_array([I(l, g, j) for l in (0, 1) for j in range(3) for g in (0, 1)]),
+                     b3=ptr_array([fp.ptr(f"transform{d}.{l}.attention.linear_layers.{j}.bias") for l in (0, 1) for j in range(3) for d in (1, 2)]),
+                     wo_img=img(3), bo=fam("transform{d}.{l}.attention.output_linear.bias"),
+                     la2=fam("transform{d}.{l}.output_sublayer.norm.a_2"), lb2=fam("transform{d}.{l}.output_sublayer.norm.b_2"),
+                     w1_img=img(4), b1=fam("transform{d}.{l}.feed_forward.w_1.bias"), w2_img=img(8), b2=fam("transform{d}.{l}.feed_forward.w_2.bias"))
             self._ptr_cache["bert_seq_infer"] = c
         return c
 
@@ -437,8 +438,8 @@ class Bert4recEngine(SasrecEngine):
             self._enqueue_eval_images(pl)
         pl.tiles_written = False
         if self._eval_one_launch(pl):
-            L.call("amid_bert_seq_fwd_gather_infer_f32", pl.x[2].data_ptr(), *self._seq_infer_ptrs(), B, T, lf, self.table.data_ptr(), self.n_rows,
-                   pl.idx_all.data_ptr(), pl.in_seq_d2.data_ptr(), s)
+            L.call_named("amid_bert_seq_fwd_gather_infer_f32", self._seq_infer_ptrs(), x_out=pl.x[2].data_ptr(), B=B, T=T, live=lf,
+                         table=self.table.data_ptr(), n_rows=self.n_rows, idx_all=pl.idx_all.data_ptr(), seq_d2=pl.in_seq_d2.data_ptr(), stream=s)
             return
         if self.comp:
             self._enqueue_comp_front(pl, gather_items=False)
@@ -493,10 +494,10 @@ class Bert4recEngine(SasrecEngine):
                    pl.dp1.data_ptr(), pl.dp2.data_ptr(), pl.loss_part.data_ptr(), pl.dxbuf.data_ptr(), ditems, None, pl.sc_part.data_ptr(),
                    None, None, 0, s)
         else:
-            L.call("amid_head_bwd_f32", pl.x[2].data_ptr(), None, pl.u.data_ptr(), items, fp.ptr("predictModule.fc.0.weight"),
-               fp.ptr("predictModule.fc.0.bias"), fp.ptr("predictModule.fc.2.weight"), fp.ptr("predictModule.fc.2.bias"), pl.p1.data_ptr(),
-               pl.p2.data_ptr(), pl.dp1.data_ptr(), pl.dp2.data_ptr(), B, T, NI, D, self.hid, 0.0, pl.dxbuf.data_ptr(), ditems, None,
-               pl.sc_part.data_ptr(), None, None, 0, s)
+            L.call_named("amid_head_bwd_f32", self._scorer(), x=pl.x[2].data_ptr(), ln_w=None, u=pl.u.data_ptr(), items=items, p1=pl.p1.data_ptr(),
+                         p2=pl.p2.data_ptr(), dp1=pl.dp1.data_ptr(), dp2=pl.dp2.data_ptr(), B=B, T=T, NI=NI, D=D, hid=self.hid, eps=0.0,
+                         dx=pl.dxbuf.data_ptr(), ditems=ditems, ln_part=None, sc_part=pl.sc_part.data_ptr(), tr_src=None, tr_dst=None, n_tr=0,
+                         stream=s)
         # the train step's own backward walks the LIVE sequences only (the loss sends no gradient into the other domain's encoder of a
         # sample); a comp module in front of the encoders reads the gradient of EVERY encoder-input row: all rows then
         lv = None if self.comp else self._live_list(pl)
