@@ -175,9 +175,5 @@ extern "C" int amid_bert_seq_fwd_gather_infer_f32(float* x_out, const float* con
     if (2LL * B * T * BSD * 4 > 0x7FFFFFF0LL) return AMID_ERR_UNSUPPORTED;      // the [2, B, T, 128] output goes through a buffer descriptor: 2 GiB
     a.x_out = x_out; a.table = table; a.n_rows = n_rows; a.idx = idx_all; a.seq_d2 = seq_d2; a.live = live; a.B = B; a.T = T;
     a.att_scale = sqrtf((float)(BSD / 4));                                  // attention.hip attn_fill: sqrt(d_k) for the bidirectional core
-    static unsigned long long attr_done = 0;
-    if (int rc = lds_attr_once((const void*)bert_seq_infer_kernel, strip_lds_bytes<BSD>(), attr_done)) return rc;
-    bert_seq_infer_kernel<<<B, STRIP_THREADS, strip_lds_bytes<BSD>(), (hipStream_t)stream>>>(a);
-    AMID_LAUNCH_CHECK();
-    return AMID_OK;
+    return launch_lds<bert_seq_infer_kernel>(B, STRIP_THREADS, strip_lds_bytes<BSD>(), stream, a);
 }

@@ -328,59 +328,61 @@ static void fill_bqkv(BStripQkvArgs& a, const float* x, const float* const* la, 
     }
 }
 
-static int bqkv_fwd(const float* x, const float* const* la, const float* const* lb, const float* const* w3, const float* const* b3, int B,
-                    int T, const int* live, float* y, float* q, float* k, float* v, const BPrologue& pro, void* stream, int mode = 0) {
-    AMID_CHECK_ARG(x && la && lb && w3 && b3 && q && k && v);       // (y == NULL: not stored)
-    BStripQkvArgs a;
-    fill_bqkv(a, x, la, lb, w3, b3, y, q, k, v);
-    StripGeom sg;
-    if (int e = bert_strip_geom(B, T, live, &sg)) return e;
-    static unsigned long long attr_done[2] = {0, 0};
-    if (mode == 3) {
-        if (int rc = lds_attr_once((const void*)bert_strip_qkv_fwd_kernel<3>, strip_lds_bytes<BSD>(), attr_done[1])) return rc;
-        bert_strip_qkv_fwd_kernel<3><<<2 * sg.tpg + pro.blocks, STRIP_THREADS, strip_lds_bytes<BSD>(), (hipStream_t)stream>>>(a, sg, pro);
-    } else {
-        if (int rc = lds_attr_once((const void*)bert_strip_qkv_fwd_kernel<0>, strip_lds_bytes<BSD>(), attr_done[0])) return rc;
-        bert_strip_qkv_fwd_kernel<0><<<2 * sg.tpg + pro.blocks, STRIP_THREADS, strip_lds_bytes<BSD>(), (hipStream_t)stream>>>(a, sg, pro);
+// how a launch multiplies: fp32 matrix instructions on the fp32 weights, or fp32 operands as three bf16 pieces on the weights' three-plane
+// tile images (amid_bert_weight_images_f32; the *_p3_f32 entries) -- the values are the kernels' MODE
+enum BProducts { B_FP32 = 0, B_PIECES3 = 3 };
+
+// LayerNorm + q / k / v of a block as its entries state it (every field null / zero unless named).  w3 / b3: host arrays of six device
+// pointers ordered [q, k, v][domain] (as amid_bert_qkv_fwd_f32).  y == NULL: LNb_in(x) is not stored (an inference forward: nobody reads it).
+// Optional, the step's prologue riding as extra workgroups: key_keep[i] = seq_d2[i] > 0 for i < n_keys (seq_d2 == NULL: none), and
+// tr_dst[m][c][r] = tr_src[m][r][c] for n_tr <= 24 matrices of tr_rows[m] x tr_cols[m] floats (multiples of 64) -- what amid_key_keep_u8 and
+// amid_transpose_rect_f32 do in launches of their own
+struct BQkvFwdCall {
+    const float* x = nullptr; FamC la = nullptr, lb = nullptr, w3 = nullptr, b3 = nullptr;
+    int B = 0, T = 0; const int* live = nullptr;
+    float* y = nullptr; float* q = nullptr; float* k = nullptr; float* v = nullptr;
+    const long long* seq_d2 = nullptr; int n_keys = 0; unsigned char* key_keep = nullptr;
+    FamC tr_src = nullptr; Fam tr_dst = nullptr; const int* tr_rows = nullptr; const int* tr_cols = nullptr; int n_tr = 0;
+    BProducts products = B_FP32; void* stream = nullptr;
+};
+#define BQKV_FWD_CALL(c, w3_) BQkvFwdCall c; c.x = x; c.la = la; c.lb = lb; c.w3 = w3_; c.b3 = b3; c.B = B; c.T = T; c.live = live; c.y = y; c.q = q; c.k = k; c.v = v; c.stream = stream
+#define BQKV_FWD_PRO(c)                                                                                                                         \
+    c.seq_d2 = seq_d2; c.n_keys = n_keys; c.key_keep = key_keep; c.tr_src = tr_src; c.tr_dst = tr_dst; c.tr_rows = tr_rows; c.tr_cols = tr_cols; \
+    c.n_tr = n_tr
+
+static int bqkv_fwd(const BQkvFwdCall& c) {
+    AMID_CHECK_ARG(c.n_tr >= 0 && c.n_tr <= BPRO_MAX && (c.n_tr == 0 || (c.tr_src && c.tr_dst && c.tr_rows && c.tr_cols)));
+    AMID_CHECK_ARG(c.seq_d2 == nullptr || (c.key_keep != nullptr && c.n_keys > 0));
+    BPrologue pro = {};
+    pro.seq = c.seq_d2; pro.keep = c.key_keep; pro.n_keys = c.n_keys; pro.n = c.n_tr;
+    for (int i = 0; i < c.n_tr; ++i) {
+        AMID_CHECK_ARG(c.tr_src[i] && c.tr_dst[i] && c.tr_rows[i] > 0 && c.tr_cols[i] > 0 && c.tr_rows[i] % 64 == 0 && c.tr_cols[i] % 64 == 0);
+        pro.src[i] = c.tr_src[i]; pro.dst[i] = c.tr_dst[i]; pro.rows[i] = c.tr_rows[i]; pro.cols[i] = c.tr_cols[i];
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AMID_OK : (int)e;
+    pro.blocks = (c.seq_d2 != nullptr || c.n_tr > 0) ? 96 : 0;
+    AMID_CHECK_ARG(c.x && c.la && c.lb && c.w3 && c.b3 && c.q && c.k && c.v);       // (y == NULL: not stored)
+    BStripQkvArgs a;
+    fill_bqkv(a, c.x, c.la, c.lb, c.w3, c.b3, c.y, c.q, c.k, c.v);
+    StripGeom sg;
+    if (int e = bert_strip_geom(c.B, c.T, c.live, &sg)) return e;
+    const int grid = 2 * sg.tpg + pro.blocks;
+    return c.products == B_PIECES3 ? launch_lds<bert_strip_qkv_fwd_kernel<3>>(grid, STRIP_THREADS, strip_lds_bytes<BSD>(), c.stream, a, sg, pro)
+                                   : launch_lds<bert_strip_qkv_fwd_kernel<0>>(grid, STRIP_THREADS, strip_lds_bytes<BSD>(), c.stream, a, sg, pro);
 }
 
-// w3 / b3: host arrays of six device pointers ordered [q, k, v][domain] (as amid_bert_qkv_fwd_f32).  y == NULL: LNb_in(x) is not stored (an
-// inference forward: nobody reads it)
 extern "C" int amid_bert_strip_qkv_fwd_f32(const float* x, const float* const* la, const float* const* lb, const float* const* w3,
                                            const float* const* b3, int B, int T, const int* live, float* y, float* q, float* k, float* v,
                                            void* stream) {
-    BPrologue pro = {};
-    return bqkv_fwd(x, la, lb, w3, b3, B, T, live, y, q, k, v, pro, stream);
-}
-
-// ... with the step's prologue riding as extra workgroups: key_keep[i] = seq_d2[i] > 0 for i < n_keys (seq_d2 == NULL: none), and
-// tr_dst[m][c][r] = tr_src[m][r][c] for n_tr <= 24 matrices of tr_rows[m] x tr_cols[m] floats (multiples of 64) -- what
-// amid_key_keep_u8 and amid_transpose_rect_f32 do in launches of their own
-static int bqkv_fwd_pro(const float* x, const float* const* la, const float* const* lb, const float* const* w3,
-                        const float* const* b3, int B, int T, const int* live, float* y, float* q, float* k,
-                        float* v, const long long* seq_d2, int n_keys, unsigned char* key_keep,
-                        const float* const* tr_src, float* const* tr_dst, const int* tr_rows, const int* tr_cols,
-                        int n_tr, void* stream, int mode) {
-    AMID_CHECK_ARG(n_tr >= 0 && n_tr <= BPRO_MAX && (n_tr == 0 || (tr_src && tr_dst && tr_rows && tr_cols)));
-    AMID_CHECK_ARG(seq_d2 == nullptr || (key_keep != nullptr && n_keys > 0));
-    BPrologue pro = {};
-    pro.seq = seq_d2; pro.keep = key_keep; pro.n_keys = n_keys; pro.n = n_tr;
-    for (int i = 0; i < n_tr; ++i) {
-        AMID_CHECK_ARG(tr_src[i] && tr_dst[i] && tr_rows[i] > 0 && tr_cols[i] > 0 && tr_rows[i] % 64 == 0 && tr_cols[i] % 64 == 0);
-        pro.src[i] = tr_src[i]; pro.dst[i] = tr_dst[i]; pro.rows[i] = tr_rows[i]; pro.cols[i] = tr_cols[i];
-    }
-    pro.blocks = (seq_d2 != nullptr || n_tr > 0) ? 96 : 0;
-    return bqkv_fwd(x, la, lb, w3, b3, B, T, live, y, q, k, v, pro, stream, mode);
+    BQKV_FWD_CALL(c, w3);
+    return bqkv_fwd(c);
 }
 extern "C" int amid_bert_strip_qkv_fwd_pro_f32(const float* x, const float* const* la, const float* const* lb, const float* const* w3,
                                                const float* const* b3, int B, int T, const int* live, float* y, float* q, float* k,
                                                float* v, const long long* seq_d2, int n_keys, unsigned char* key_keep,
                                                const float* const* tr_src, float* const* tr_dst, const int* tr_rows, const int* tr_cols,
                                                int n_tr, void* stream) {
-    return bqkv_fwd_pro(x, la, lb, w3, b3, B, T, live, y, q, k, v, seq_d2, n_keys, key_keep, tr_src, tr_dst, tr_rows, tr_cols, n_tr, stream, 0);
+    BQKV_FWD_CALL(c, w3); BQKV_FWD_PRO(c);
+    return bqkv_fwd(c);
 }
 // ... on bf16 pieces: w3 = the tiles' three-plane images (amid_bert_weight_images_f32), everything else as above
 extern "C" int amid_bert_strip_qkv_fwd_pro_p3_f32(const float* x, const float* const* la, const float* const* lb, const float* const* w3_img,
@@ -388,41 +390,53 @@ extern "C" int amid_bert_strip_qkv_fwd_pro_p3_f32(const float* x, const float* c
                                                   float* v, const long long* seq_d2, int n_keys, unsigned char* key_keep,
                                                   const float* const* tr_src, float* const* tr_dst, const int* tr_rows, const int* tr_cols,
                                                   int n_tr, void* stream) {
-    return bqkv_fwd_pro(x, la, lb, w3_img, b3, B, T, live, y, q, k, v, seq_d2, n_keys, key_keep, tr_src, tr_dst, tr_rows, tr_cols, n_tr, stream, 3);
+    BQKV_FWD_CALL(c, w3_img); BQKV_FWD_PRO(c); c.products = B_PIECES3;
+    return bqkv_fwd(c);
 }
+#undef BQKV_FWD_PRO
+#undef BQKV_FWD_CALL
 
 // out-projection + feed-forward of a block; nla != NULL: the next block's LayerNorm + q / k / v on x2 in the same launch (x2 is
 // then also the next block's saved input).  x1, y2, pre, h, ny: each may be NULL = not stored (an inference forward)
-static int boproj_ffn_fwd(const float* o, const float* x, const float* const* wo, const float* const* bo,
-                          const float* const* la, const float* const* lb, const float* const* w1,
-                          const float* const* b1, const float* const* w2, const float* const* b2, int B, int T,
-                          const int* live, int layer, const void* step_state, int train, float p_drop, float* x1,
-                          float* y2, float* pre, float* h, float* x2, const float* const* nla,
-                          const float* const* nlb, const float* const* nw3, const float* const* nb3, float* ny,
-                          float* nq, float* nk, float* nv, void* stream, int mode) {
-    AMID_CHECK_ARG(o && x && wo && bo && la && lb && w1 && b1 && w2 && b2 && x2 && (!train || step_state));      // (x1, y2, pre, h == NULL: not stored)
-    const bool next = nla != nullptr;
-    AMID_CHECK_ARG(!next || (nlb && nw3 && nb3 && nq && nk && nv));
+struct BOffCall {
+    const float* o = nullptr; const float* x = nullptr;
+    FamC wo = nullptr, bo = nullptr, la = nullptr, lb = nullptr, w1 = nullptr, b1 = nullptr, w2 = nullptr, b2 = nullptr;
+    int B = 0, T = 0; const int* live = nullptr;
+    int layer = 0; const void* step_state = nullptr; int train = 0; float p_drop = 0.f;
+    float* x1 = nullptr; float* y2 = nullptr; float* pre = nullptr; float* h = nullptr; float* x2 = nullptr;
+    FamC nla = nullptr, nlb = nullptr, nw3 = nullptr, nb3 = nullptr;
+    float* ny = nullptr; float* nq = nullptr; float* nk = nullptr; float* nv = nullptr;
+    BProducts products = B_FP32; void* stream = nullptr;
+};
+#define BOFF_CALL(c, wo_, w1_, w2_, nw3_)                                                                                                       \
+    BOffCall c;                                                                                                                                 \
+    c.o = o; c.x = x; c.wo = wo_; c.bo = bo; c.la = la; c.lb = lb; c.w1 = w1_; c.b1 = b1; c.w2 = w2_; c.b2 = b2; c.B = B; c.T = T; c.live = live;   \
+    c.layer = layer; c.step_state = step_state; c.train = train; c.p_drop = p_drop; c.x1 = x1; c.y2 = y2; c.pre = pre; c.h = h; c.x2 = x2;       \
+    c.nla = nla; c.nlb = nlb; c.nw3 = nw3_; c.nb3 = nb3; c.ny = ny; c.nq = nq; c.nk = nk; c.nv = nv; c.stream = stream
+
+static int boproj_ffn_fwd(const BOffCall& c) {
+    AMID_CHECK_ARG(c.o && c.x && c.wo && c.bo && c.la && c.lb && c.w1 && c.b1 && c.w2 && c.b2 && c.x2 && (!c.train || c.step_state));      // (x1, y2, pre, h == NULL: not stored)
+    const bool next = c.nla != nullptr;
+    AMID_CHECK_ARG(!next || (c.nlb && c.nw3 && c.nb3 && c.nq && c.nk && c.nv));
     BStripOffArgs a;
-    a.o = o; a.x = x; a.x1 = x1; a.y2 = y2; a.pre = pre; a.h = h; a.x2 = x2;
-    a.st = (const StepState*)step_state; a.layer = layer;
-    a.train = (train && p_drop > 0.f) ? 1 : 0;
-    a.spec = drop_spec(p_drop);
+    a.o = c.o; a.x = c.x; a.x1 = c.x1; a.y2 = c.y2; a.pre = c.pre; a.h = c.h; a.x2 = c.x2;
+    a.st = (const StepState*)c.step_state; a.layer = c.layer;
+    const DropoutArgs d = dropout_args(c.train, c.p_drop);
+    a.train = d.train; a.spec = d.spec; a.scale = d.scale;
     if (a.train && spec_bits(a.spec) != 16) return AMID_ERR_UNSUPPORTED;      // KeepGen: the 16-bit decisions of p = 0.1 (the reference's rate, model_seq.py:267)
-    a.scale = a.train ? 1.0f / (1.0f - p_drop) : 1.0f;
     for (int g = 0; g < 2; ++g) {
-        a.wo[g] = wo[g]; a.bo[g] = bo[g]; a.la[g] = la[g]; a.lb[g] = lb[g];
-        a.w1[g] = w1[g]; a.b1[g] = b1[g]; a.w2[g] = w2[g]; a.b2[g] = b2[g];
+        a.wo[g] = c.wo[g]; a.bo[g] = c.bo[g]; a.la[g] = c.la[g]; a.lb[g] = c.lb[g];
+        a.w1[g] = c.w1[g]; a.b1[g] = c.b1[g]; a.w2[g] = c.w2[g]; a.b2[g] = c.b2[g];
     }
     BStripQkvArgs nx = {};
-    if (next) fill_bqkv(nx, x2, nla, nlb, nw3, nb3, ny, nq, nk, nv);
+    if (next) fill_bqkv(nx, c.x2, c.nla, c.nlb, c.nw3, c.nb3, c.ny, c.nq, c.nk, c.nv);
     StripGeom sg;
-    if (int e = bert_strip_geom(B, T, live, &sg)) return e;
-    if (mode == 3)
-        return next ? launch_strip<bert_strip_oproj_ffn_fwd_kernel<true, 3>, BSD>(sg, stream, a, nx)
-                    : launch_strip<bert_strip_oproj_ffn_fwd_kernel<false, 3>, BSD>(sg, stream, a, nx);
-    return next ? launch_strip<bert_strip_oproj_ffn_fwd_kernel<true, 0>, BSD>(sg, stream, a, nx)
-                : launch_strip<bert_strip_oproj_ffn_fwd_kernel<false, 0>, BSD>(sg, stream, a, nx);
+    if (int e = bert_strip_geom(c.B, c.T, c.live, &sg)) return e;
+    if (c.products == B_PIECES3)
+        return next ? launch_strip<bert_strip_oproj_ffn_fwd_kernel<true, 3>, BSD>(sg, c.stream, a, nx)
+                    : launch_strip<bert_strip_oproj_ffn_fwd_kernel<false, 3>, BSD>(sg, c.stream, a, nx);
+    return next ? launch_strip<bert_strip_oproj_ffn_fwd_kernel<true, 0>, BSD>(sg, c.stream, a, nx)
+                : launch_strip<bert_strip_oproj_ffn_fwd_kernel<false, 0>, BSD>(sg, c.stream, a, nx);
 }
 extern "C" int amid_bert_strip_oproj_ffn_fwd_f32(const float* o, const float* x, const float* const* wo, const float* const* bo,
                                                  const float* const* la, const float* const* lb, const float* const* w1,
@@ -431,8 +445,8 @@ extern "C" int amid_bert_strip_oproj_ffn_fwd_f32(const float* o, const float* x,
                                                  float* y2, float* pre, float* h, float* x2, const float* const* nla,
                                                  const float* const* nlb, const float* const* nw3, const float* const* nb3, float* ny,
                                                  float* nq, float* nk, float* nv, void* stream) {
-    return boproj_ffn_fwd(o, x, wo, bo, la, lb, w1, b1, w2, b2, B, T, live, layer, step_state, train, p_drop, x1, y2, pre, h, x2, nla, nlb, nw3, nb3,
-                          ny, nq, nk, nv, stream, 0);
+    BOFF_CALL(c, wo, w1, w2, nw3);
+    return boproj_ffn_fwd(c);
 }
 // ... on bf16 pieces: wo / nw3 = tile images, w1 / w2 = the first of their four tiles' images (one behind the other)
 extern "C" int amid_bert_strip_oproj_ffn_fwd_p3_f32(const float* o, const float* x, const float* const* wo_img, const float* const* bo,
@@ -442,85 +456,100 @@ extern "C" int amid_bert_strip_oproj_ffn_fwd_p3_f32(const float* o, const float*
                                                     float* y2, float* pre, float* h, float* x2, const float* const* nla,
                                                     const float* const* nlb, const float* const* nw3_img, const float* const* nb3, float* ny,
                                                     float* nq, float* nk, float* nv, void* stream) {
-    return boproj_ffn_fwd(o, x, wo_img, bo, la, lb, w1_img, b1, w2_img, b2, B, T, live, layer, step_state, train, p_drop, x1, y2, pre, h, x2, nla, nlb,
-                          nw3_img, nb3, ny, nq, nk, nv, stream, 3);
+    BOFF_CALL(c, wo_img, w1_img, w2_img, nw3_img); c.products = B_PIECES3;
+    return boproj_ffn_fwd(c);
 }
+#undef BOFF_CALL
 
-static int fill_bffn_bwd(BStripFfnBwdArgs& a, const float* dx2, const float* pre, const float* x1, const float* const* la,
-                         const float* const* w2T, const float* const* w1T, const float* const* woT, int layer, const void* step_state,
-                         int train, float p_drop, float* dz, float* dpre, float* dx1, float* dt, float* d_o, float* ln_part) {
-    AMID_CHECK_ARG(pre && x1 && la && w2T && w1T && woT && dz && dpre && dx1 && dt && d_o && ln_part && (!train || step_state));
-    a.dx2 = dx2; a.pre = pre; a.x1 = x1; a.dz = dz; a.dpre = dpre; a.dx1 = dx1; a.dt = dt; a.d_o = d_o; a.ln_part = ln_part;
-    a.st = (const StepState*)step_state; a.layer = layer;
-    a.train = (train && p_drop > 0.f) ? 1 : 0;
-    a.spec = drop_spec(p_drop);
+// the feed-forward / out-projection backward of a block as an entry states it; inside BQkvBwdCall the optional fused block (absent: pre == NULL)
+struct BFfnBwdCall {
+    const float* dx2 = nullptr; const float* pre = nullptr; const float* x1 = nullptr;
+    FamC la = nullptr, w2T = nullptr, w1T = nullptr, woT = nullptr;
+    int layer = 0; const void* step_state = nullptr; int train = 0; float p_drop = 0.f;
+    float* dz = nullptr; float* dpre = nullptr; float* dx1 = nullptr; float* dt = nullptr; float* d_o = nullptr; float* ln_part = nullptr;
+};
+// what every backward strip launch of a block is given besides its operands
+struct BBwdLaunch { int B = 0, T = 0; const int* live = nullptr; BProducts products = B_FP32; void* stream = nullptr; };
+#define BBWD_LAUNCH(l, products_) BBwdLaunch l; l.B = B; l.T = T; l.live = live; l.products = products_; l.stream = stream
+
+static int fill_bffn_bwd(BStripFfnBwdArgs& a, const BFfnBwdCall& c) {
+    AMID_CHECK_ARG(c.pre && c.x1 && c.la && c.w2T && c.w1T && c.woT && c.dz && c.dpre && c.dx1 && c.dt && c.d_o && c.ln_part && (!c.train || c.step_state));
+    a.dx2 = c.dx2; a.pre = c.pre; a.x1 = c.x1; a.dz = c.dz; a.dpre = c.dpre; a.dx1 = c.dx1; a.dt = c.dt; a.d_o = c.d_o; a.ln_part = c.ln_part;
+    a.st = (const StepState*)c.step_state; a.layer = c.layer;
+    const DropoutArgs d = dropout_args(c.train, c.p_drop);
+    a.train = d.train; a.spec = d.spec; a.scale = d.scale;
     if (a.train && spec_bits(a.spec) != 16) return AMID_ERR_UNSUPPORTED;
-    a.scale = a.train ? 1.0f / (1.0f - p_drop) : 1.0f;
-    for (int g = 0; g < 2; ++g) { a.la[g] = la[g]; a.w2T[g] = w2T[g]; a.w1T[g] = w1T[g]; a.woT[g] = woT[g]; }
+    for (int g = 0; g < 2; ++g) { a.la[g] = c.la[g]; a.w2T[g] = c.w2T[g]; a.w1T[g] = c.w1T[g]; a.woT[g] = c.woT[g]; }
     return AMID_OK;
 }
 
 // ln_part: [2 * ceil(B T / amid_sas_strip_tile_rows())][2][128]; domain g's partial sums are slots [g * tpg, (g + 1) * tpg)
-static int bffn_bwd(const float* dx2, const float* pre, const float* x1, const float* const* la,
-                    const float* const* w2T, const float* const* w1T, const float* const* woT, int B, int T,
-                    const int* live, int layer, const void* step_state, int train, float p_drop, float* dz,
-                    float* dpre, float* dx1, float* dt, float* d_o, float* ln_part, void* stream, int mode) {
-    AMID_CHECK_ARG(dx2);
+static int bffn_bwd(const BFfnBwdCall& c, const BBwdLaunch& l) {
+    AMID_CHECK_ARG(c.dx2);
     BStripFfnBwdArgs a;
-    if (int e = fill_bffn_bwd(a, dx2, pre, x1, la, w2T, w1T, woT, layer, step_state, train, p_drop, dz, dpre, dx1, dt, d_o, ln_part)) return e;
+    if (int e = fill_bffn_bwd(a, c)) return e;
     StripGeom sg;
-    if (int e = bert_strip_geom(B, T, live, &sg)) return e;
-    return mode == 3 ? launch_strip<bert_strip_ffn_bwd_kernel<3>, BSD>(sg, stream, a) : launch_strip<bert_strip_ffn_bwd_kernel<0>, BSD>(sg, stream, a);
+    if (int e = bert_strip_geom(l.B, l.T, l.live, &sg)) return e;
+    return l.products == B_PIECES3 ? launch_strip<bert_strip_ffn_bwd_kernel<3>, BSD>(sg, l.stream, a) : launch_strip<bert_strip_ffn_bwd_kernel<0>, BSD>(sg, l.stream, a);
 }
+#define BFFN_BWD_CALL(c, w2T_, w1T_, woT_)                                                                                                      \
+    BFfnBwdCall c;                                                                                                                              \
+    c.dx2 = dx2; c.pre = pre; c.x1 = x1; c.la = la; c.w2T = w2T_; c.w1T = w1T_; c.woT = woT_; c.layer = layer; c.step_state = step_state;          \
+    c.train = train; c.p_drop = p_drop; c.dz = dz; c.dpre = dpre; c.dx1 = dx1; c.dt = dt; c.d_o = d_o; c.ln_part = ln_part
 extern "C" int amid_bert_strip_ffn_bwd_f32(const float* dx2, const float* pre, const float* x1, const float* const* la,
                                            const float* const* w2T, const float* const* w1T, const float* const* woT, int B, int T,
                                            const int* live, int layer, const void* step_state, int train, float p_drop, float* dz,
                                            float* dpre, float* dx1, float* dt, float* d_o, float* ln_part, void* stream) {
-    return bffn_bwd(dx2, pre, x1, la, w2T, w1T, woT, B, T, live, layer, step_state, train, p_drop, dz, dpre, dx1, dt, d_o, ln_part, stream, 0);
+    BFFN_BWD_CALL(c, w2T, w1T, woT); BBWD_LAUNCH(l, B_FP32);
+    return bffn_bwd(c, l);
 }
 // ... on bf16 pieces: w2T / w1T = the first of the four TRANSPOSED tiles' images, woT = the transposed tile's image
 extern "C" int amid_bert_strip_ffn_bwd_p3_f32(const float* dx2, const float* pre, const float* x1, const float* const* la,
                                               const float* const* w2T_img, const float* const* w1T_img, const float* const* woT_img, int B, int T,
                                               const int* live, int layer, const void* step_state, int train, float p_drop, float* dz,
                                               float* dpre, float* dx1, float* dt, float* d_o, float* ln_part, void* stream) {
-    return bffn_bwd(dx2, pre, x1, la, w2T_img, w1T_img, woT_img, B, T, live, layer, step_state, train, p_drop, dz, dpre, dx1, dt, d_o, ln_part, stream, 3);
+    BFFN_BWD_CALL(c, w2T_img, w1T_img, woT_img); BBWD_LAUNCH(l, B_PIECES3);
+    return bffn_bwd(c, l);
 }
+#undef BFFN_BWD_CALL
 
-// wT3: six device pointers ordered [q, k, v][domain] (transposed weights).  fpre != NULL: the block below's feed-forward /
-// out-projection backward (f* arguments, as amid_bert_strip_ffn_bwd_f32 without dx2) runs on d x in the same launch; dx is then not written.
+// wT3: six device pointers ordered [q, k, v][domain] (transposed weights).  ffn.pre != NULL: the block below's feed-forward /
+// out-projection backward (as amid_bert_strip_ffn_bwd_f32 without dx2) runs on d x in the same launch; dx is then not written.
 // zero_dead (with a live list and dx): the rows of dx that belong to the sequences NOT on the list are zero-filled by extra workgroups
-static int bqkv_bwd(const float* dq, const float* dk, const float* dv, const float* dx1, const float* x,
-                    const float* const* la, const float* const* wT3, int B, int T, const int* live, float* dx,
-                    int zero_dead, float* ln_part, const float* fpre, const float* fx1, const float* const* fla,
-                    const float* const* fw2T, const float* const* fw1T, const float* const* fwoT, int flayer,
-                    const void* step_state, int train, float p_drop, float* fdz, float* fdpre, float* fdx1,
-                    float* fdt, float* fd_o, float* fln_part, void* stream, int mode) {
-    AMID_CHECK_ARG(dq && dk && dv && dx1 && x && la && wT3 && ln_part);
-    const bool ffn = fpre != nullptr;
-    AMID_CHECK_ARG(ffn || dx);
+struct BQkvBwdCall {
+    const float* dq = nullptr; const float* dk = nullptr; const float* dv = nullptr; const float* dx1 = nullptr; const float* x = nullptr;
+    FamC la = nullptr, wT3 = nullptr;
+    float* dx = nullptr; int zero_dead = 0; float* ln_part = nullptr;
+    BFfnBwdCall ffn;
+};
+#define BQKV_BWD_CALL(c, wT3_, fw2T_, fw1T_, fwoT_)                                                                                             \
+    BQkvBwdCall c;                                                                                                                              \
+    c.dq = dq; c.dk = dk; c.dv = dv; c.dx1 = dx1; c.x = x; c.la = la; c.wT3 = wT3_; c.dx = dx; c.zero_dead = zero_dead; c.ln_part = ln_part;        \
+    c.ffn.pre = fpre; c.ffn.x1 = fx1; c.ffn.la = fla; c.ffn.w2T = fw2T_; c.ffn.w1T = fw1T_; c.ffn.woT = fwoT_; c.ffn.layer = flayer;               \
+    c.ffn.step_state = step_state; c.ffn.train = train; c.ffn.p_drop = p_drop; c.ffn.dz = fdz; c.ffn.dpre = fdpre; c.ffn.dx1 = fdx1;              \
+    c.ffn.dt = fdt; c.ffn.d_o = fd_o; c.ffn.ln_part = fln_part
+
+static int bqkv_bwd(const BQkvBwdCall& c, const BBwdLaunch& l) {
+    AMID_CHECK_ARG(c.dq && c.dk && c.dv && c.dx1 && c.x && c.la && c.wT3 && c.ln_part);
+    const bool ffn = c.ffn.pre != nullptr;
+    AMID_CHECK_ARG(ffn || c.dx);
     BStripQkvBwdArgs a;
-    a.dq = dq; a.dk = dk; a.dv = dv; a.dx1 = dx1; a.x = x; a.dx = dx; a.ln_part = ln_part;
+    a.dq = c.dq; a.dk = c.dk; a.dv = c.dv; a.dx1 = c.dx1; a.x = c.x; a.dx = c.dx; a.ln_part = c.ln_part;
     for (int g = 0; g < 2; ++g) {
-        a.la[g] = la[g];
-        for (int j = 0; j < 3; ++j) a.wT[j][g] = wT3[j * 2 + g];
+        a.la[g] = c.la[g];
+        for (int j = 0; j < 3; ++j) a.wT[j][g] = c.wT3[j * 2 + g];
     }
     BStripFfnBwdArgs f = {};
-    if (ffn) if (int e = fill_bffn_bwd(f, nullptr, fpre, fx1, fla, fw2T, fw1T, fwoT, flayer, step_state, train, p_drop, fdz, fdpre, fdx1, fdt, fd_o, fln_part)) return e;
+    if (ffn) if (int e = fill_bffn_bwd(f, c.ffn)) return e;
     StripGeom sg;
-    if (int e = bert_strip_geom(B, T, live, &sg)) return e;
-    a.zero_blocks = (zero_dead && live != nullptr && !ffn) ? (B < 256 ? B : 256) : 0;
-    if (ffn) return mode == 3 ? launch_strip<bert_strip_qkv_bwd_kernel<true, 3>, BSD>(sg, stream, a, f)
-                              : launch_strip<bert_strip_qkv_bwd_kernel<true, 0>, BSD>(sg, stream, a, f);
-    static unsigned long long attr_done[2] = {0, 0};
-    if (mode == 3) {
-        if (int rc = lds_attr_once((const void*)bert_strip_qkv_bwd_kernel<false, 3>, strip_lds_bytes<BSD>(), attr_done[1])) return rc;
-        bert_strip_qkv_bwd_kernel<false, 3><<<2 * sg.tpg + a.zero_blocks, STRIP_THREADS, strip_lds_bytes<BSD>(), (hipStream_t)stream>>>(a, f, sg);
-    } else {
-        if (int rc = lds_attr_once((const void*)bert_strip_qkv_bwd_kernel<false, 0>, strip_lds_bytes<BSD>(), attr_done[0])) return rc;
-        bert_strip_qkv_bwd_kernel<false, 0><<<2 * sg.tpg + a.zero_blocks, STRIP_THREADS, strip_lds_bytes<BSD>(), (hipStream_t)stream>>>(a, f, sg);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AMID_OK : (int)e;
+    if (int e = bert_strip_geom(l.B, l.T, l.live, &sg)) return e;
+    a.zero_blocks = (c.zero_dead && l.live != nullptr && !ffn) ? (l.B < 256 ? l.B : 256) : 0;
+    const bool p3 = l.products == B_PIECES3;
+    if (ffn) return p3 ? launch_strip<bert_strip_qkv_bwd_kernel<true, 3>, BSD>(sg, l.stream, a, f)
+                       : launch_strip<bert_strip_qkv_bwd_kernel<true, 0>, BSD>(sg, l.stream, a, f);
+    const int grid = 2 * sg.tpg + a.zero_blocks;
+    return p3 ? launch_lds<bert_strip_qkv_bwd_kernel<false, 3>>(grid, STRIP_THREADS, strip_lds_bytes<BSD>(), l.stream, a, f, sg)
+              : launch_lds<bert_strip_qkv_bwd_kernel<false, 0>>(grid, STRIP_THREADS, strip_lds_bytes<BSD>(), l.stream, a, f, sg);
 }
 extern "C" int amid_bert_strip_qkv_bwd_f32(const float* dq, const float* dk, const float* dv, const float* dx1, const float* x,
                                            const float* const* la, const float* const* wT3, int B, int T, const int* live, float* dx,
@@ -528,8 +557,8 @@ extern "C" int amid_bert_strip_qkv_bwd_f32(const float* dq, const float* dk, con
                                            const float* const* fw2T, const float* const* fw1T, const float* const* fwoT, int flayer,
                                            const void* step_state, int train, float p_drop, float* fdz, float* fdpre, float* fdx1,
                                            float* fdt, float* fd_o, float* fln_part, void* stream) {
-    return bqkv_bwd(dq, dk, dv, dx1, x, la, wT3, B, T, live, dx, zero_dead, ln_part, fpre, fx1, fla, fw2T, fw1T, fwoT, flayer, step_state, train, p_drop,
-                    fdz, fdpre, fdx1, fdt, fd_o, fln_part, stream, 0);
+    BQKV_BWD_CALL(c, wT3, fw2T, fw1T, fwoT); BBWD_LAUNCH(l, B_FP32);
+    return bqkv_bwd(c, l);
 }
 // ... on bf16 pieces: every weight argument = transposed tile images (as amid_bert_strip_ffn_bwd_p3_f32)
 extern "C" int amid_bert_strip_qkv_bwd_p3_f32(const float* dq, const float* dk, const float* dv, const float* dx1, const float* x,
@@ -538,9 +567,11 @@ extern "C" int amid_bert_strip_qkv_bwd_p3_f32(const float* dq, const float* dk, 
                                               const float* const* fw2T_img, const float* const* fw1T_img, const float* const* fwoT_img, int flayer,
                                               const void* step_state, int train, float p_drop, float* fdz, float* fdpre, float* fdx1,
                                               float* fdt, float* fd_o, float* fln_part, void* stream) {
-    return bqkv_bwd(dq, dk, dv, dx1, x, la, wT3_img, B, T, live, dx, zero_dead, ln_part, fpre, fx1, fla, fw2T_img, fw1T_img, fwoT_img, flayer, step_state,
-                    train, p_drop, fdz, fdpre, fdx1, fdt, fd_o, fln_part, stream, 3);
+    BQKV_BWD_CALL(c, wT3_img, fw2T_img, fw1T_img, fwoT_img); BBWD_LAUNCH(l, B_PIECES3);
+    return bqkv_bwd(c, l);
 }
+#undef BQKV_BWD_CALL
+#undef BBWD_LAUNCH
 
 // Three-plane bf16 fragment images (weights_image.h: hi + mid + lo = the fp32 element exactly) of n <= 96 weight TILES of 128 x 128: tile i
 // is src[i][r * ld[i] + c] (tr[i] = 0) or its transpose src[i][c * ld[i] + r] (tr[i] != 0), r, c < 128; dst16: [n][3][128][128] bf16.

@@ -440,91 +440,120 @@ extern "C" int amid_sas_seq_supported(int B, int T, int D, int H) {
 // (optional) = the step state whose step_done the launch re-joins
 struct SeqGather { const float* table; const int* idx; const float* pos[2]; float* items; int ni; StepState* done; };
 
-// set around a call by the *_p1_f32 entries: the pieces build multiplies ONE piece per operand (bf16 products on the three-plane images' hi planes)
-static thread_local int tl_one_piece = 0;
+// What an exported forward asks of seq_fwd_impl (host only; grouped as include/amid_hip.h groups the parameters).  Every field is null /
+// zero unless the entry point names it: a form is declared by the fields its entry sets, nowhere else.
+struct SeqFwdCall {
+    // the twelve parameter families
+    FamC ln1_w = nullptr, ln1_b = nullptr, w_in = nullptr, b_in = nullptr, w_o = nullptr, b_o = nullptr, ln2_w = nullptr, ln2_b = nullptr, w1 = nullptr,
+         b1 = nullptr, w2 = nullptr, b2 = nullptr;
+    // the layers' inputs, the output, the saved-tensor families: nine tensors a layer (qn, y) or seven and the row statistics (ln_stat)
+    FamC x_in = nullptr; float* xout = nullptr;
+    Fam qn = nullptr, q = nullptr, k = nullptr, v = nullptr, o = nullptr, stats = nullptr, r = nullptr, y = nullptr, h = nullptr, ln_stat = nullptr;
+    // shape and scalars
+    int n_layers = 0, B = 0, T = 0, D = 0, H = 0;
+    float ln_eps = 0.f;
+    const unsigned char* tmq = nullptr; const int* live = nullptr;
+    const void* step_state = nullptr; int train = 0; float p_drop = 0.f;
+    void* stream = nullptr;
+    // the weight images: bf16 fragment images of this step's weights (null: fp32 products), one plane (operands rounded to bf16) or three
+    // (fp32 operands as bf16 pieces); one_piece (the *_p1_f32 entries): the pieces build multiplies only the hi planes and hi pieces
+    const void* w16 = nullptr; int w16_planes = 1; bool one_piece = false;
+    // optional: the train step's head on the workgroups' tail, the gather as their prologue; infer: nothing saved for a backward
+    const HeadArgs* head = nullptr; const SeqGather* gather = nullptr; bool infer = false;
+};
+// A record `c` with the parameters every exported forward takes bound to its fields of the same names (a name the entry lacks does not
+// compile); SEQ_CALL_STEP: with those of the forwards a backward follows.  qn / y or ln_stat, the images, the optional blocks: named by the entry.
+#define SEQ_CALL_COMMON(c)                                                                                                                      \
+    SeqFwdCall c;                                                                                                                               \
+    c.n_layers = n_layers; c.xout = xout; c.ln1_w = ln1_w; c.ln1_b = ln1_b; c.w_in = w_in; c.b_in = b_in; c.w_o = w_o; c.b_o = b_o; c.ln2_w = ln2_w; \
+    c.ln2_b = ln2_b; c.w1 = w1; c.b1 = b1; c.w2 = w2; c.b2 = b2; c.ln_eps = ln_eps; c.B = B; c.T = T; c.D = D; c.H = H; c.live = live; c.stream = stream
+#define SEQ_CALL_STEP(c)                                                                                                                        \
+    SEQ_CALL_COMMON(c); c.x_in = x_in; c.q = q; c.k = k; c.v = v; c.o = o; c.stats = stats; c.r = r; c.h = h; c.tmq = tmq;                          \
+    c.step_state = step_state; c.train = train; c.p_drop = p_drop
+// ... and the head's operands (amid_head_fwd_bwd_own_vec_f32's) packed into `ha`: the value is head_own_vec_args' return code
+#define SEQ_HEAD_ARGS(ha)                                                                                                                       \
+    head_own_vec_args(ha, last_ln_w, last_ln_b, items, sw1, sb1, sw2, sb2, labels, domain_id, B, T, NI, D, hid, ln_eps, u, p1, p2, dp1, dp2,       \
+                      loss_part, dx, ditems, ln_part, hidg)
 
-static int seq_fwd_impl(int n_layers, const float* const* x_in, float* xout, const float* const* ln1_w, const float* const* ln1_b,
-                        const float* const* w_in, const float* const* b_in, const float* const* w_o, const float* const* b_o,
-                        const float* const* ln2_w, const float* const* ln2_b, const float* const* w1, const float* const* b1,
-                        const float* const* w2, const float* const* b2, float* const* qn, float* const* q, float* const* k,
-                        float* const* v, float* const* o, float* const* stats, float* const* r, float* const* y, float* const* h,
-                        const unsigned char* tmq, float ln_eps, int B, int T, int D, int H, const int* live,
-                        const void* step_state, int train, float p_drop, const void* w16, void* stream, int w16_planes = 1,
-                        float* const* ln_stat = nullptr, const HeadArgs* head = nullptr, bool infer = false, const SeqGather* gat = nullptr) {
-    AMID_CHECK_ARG(n_layers >= 1 && n_layers <= 2 && x_in && (xout || head) && ln1_w && ln1_b && w_in && b_in && w_o && b_o && ln2_w && ln2_b && w1 && b1 &&
-                   w2 && b2 && (!train || step_state));
-    AMID_CHECK_ARG(infer || ((ln_stat || (qn && y)) && q && k && v && o && stats && r && h));
-    if (ln_stat != nullptr && !(w16 != nullptr && w16_planes == 3 && D == 128)) return AMID_ERR_UNSUPPORTED;      // the piece forward only
+static int seq_fwd_impl(const SeqFwdCall& c) {
+    const int n_layers = c.n_layers, D = c.D;
+    const bool pieces128 = c.w16 != nullptr && c.w16_planes == 3 && D == 128;      // the producer-side pieces build
+    AMID_CHECK_ARG(n_layers >= 1 && n_layers <= 2 && c.x_in && (c.xout || c.head) && c.ln1_w && c.ln1_b && c.w_in && c.b_in && c.w_o && c.b_o && c.ln2_w &&
+                   c.ln2_b && c.w1 && c.b1 && c.w2 && c.b2 && (!c.train || c.step_state));
+    AMID_CHECK_ARG(c.infer || ((c.ln_stat || (c.qn && c.y)) && c.q && c.k && c.v && c.o && c.stats && c.r && c.h));
+    if (c.ln_stat != nullptr && !pieces128) return AMID_ERR_UNSUPPORTED;      // the piece forward only
     // an inference forward saves nothing (SeqGeom::save_bytes = 0): the producer-side pieces build at D 128 only, T a multiple-of-16 strip count it tiles
-    if (infer && !(w16 != nullptr && w16_planes == 3 && D == 128 && !train && head == nullptr)) return AMID_ERR_UNSUPPORTED;
-    if (!amid_sas_seq_supported(B, T, D, H)) return AMID_ERR_UNSUPPORTED;
+    if (c.infer && !(pieces128 && !c.train && c.head == nullptr)) return AMID_ERR_UNSUPPORTED;
+    if (!amid_sas_seq_supported(c.B, c.T, D, c.H)) return AMID_ERR_UNSUPPORTED;
     SeqFwdArgs a = {};
     a.n_layers = n_layers;
     for (int l = 0; l < n_layers; ++l) {
         SeqLayer& P = a.L[l];
         for (int g = 0; g < 2; ++g) {
             const int i = 2 * l + g;
-            AMID_CHECK_ARG(ln1_w[i] && ln1_b[i] && w_in[i] && b_in[i] && w_o[i] && b_o[i] && ln2_w[i] && ln2_b[i] && w1[i] && b1[i] && w2[i] && b2[i]);
-            P.ln1_w[g] = ln1_w[i]; P.ln1_b[g] = ln1_b[i]; P.w_in[g] = w_in[i]; P.b_in[g] = b_in[i]; P.w_o[g] = w_o[i]; P.b_o[g] = b_o[i];
-            P.ln2_w[g] = ln2_w[i]; P.ln2_b[g] = ln2_b[i]; P.w1[g] = w1[i]; P.b1[g] = b1[i]; P.w2[g] = w2[i]; P.b2[g] = b2[i];
+            AMID_CHECK_ARG(c.ln1_w[i] && c.ln1_b[i] && c.w_in[i] && c.b_in[i] && c.w_o[i] && c.b_o[i] && c.ln2_w[i] && c.ln2_b[i] && c.w1[i] && c.b1[i] &&
+                           c.w2[i] && c.b2[i]);
+            P.ln1_w[g] = c.ln1_w[i]; P.ln1_b[g] = c.ln1_b[i]; P.w_in[g] = c.w_in[i]; P.b_in[g] = c.b_in[i]; P.w_o[g] = c.w_o[i]; P.b_o[g] = c.b_o[i];
+            P.ln2_w[g] = c.ln2_w[i]; P.ln2_b[g] = c.ln2_b[i]; P.w1[g] = c.w1[i]; P.b1[g] = c.b1[i]; P.w2[g] = c.w2[i]; P.b2[g] = c.b2[i];
         }
-        if (infer) {
-            AMID_CHECK_ARG(l > 0 || x_in[0]);
-            P.x = l == 0 ? const_cast<float*>(x_in[0]) : nullptr;
+        if (c.infer) {
+            AMID_CHECK_ARG(l > 0 || c.x_in[0]);
+            P.x = l == 0 ? const_cast<float*>(c.x_in[0]) : nullptr;
             P.qn = P.q = P.k = P.v = P.o = P.stats = P.r = P.y = P.h = P.ln_stat = nullptr;
             continue;
         }
-        AMID_CHECK_ARG(x_in[l] && q[l] && k[l] && v[l] && o[l] && stats[l] && r[l] && h[l] && (ln_stat ? ln_stat[l] != nullptr : (qn[l] && y[l])));
-        P.x = const_cast<float*>(x_in[l]); P.qn = ln_stat ? nullptr : qn[l]; P.q = q[l]; P.k = k[l]; P.v = v[l]; P.o = o[l]; P.stats = stats[l];
-        P.r = r[l]; P.y = ln_stat ? nullptr : y[l]; P.h = h[l]; P.ln_stat = ln_stat ? ln_stat[l] : nullptr;
+        AMID_CHECK_ARG(c.x_in[l] && c.q[l] && c.k[l] && c.v[l] && c.o[l] && c.stats[l] && c.r[l] && c.h[l] &&
+                       (c.ln_stat ? c.ln_stat[l] != nullptr : (c.qn[l] && c.y[l])));
+        P.x = const_cast<float*>(c.x_in[l]); P.qn = c.ln_stat ? nullptr : c.qn[l]; P.q = c.q[l]; P.k = c.k[l]; P.v = c.v[l]; P.o = c.o[l];
+        P.stats = c.stats[l]; P.r = c.r[l]; P.y = c.ln_stat ? nullptr : c.y[l]; P.h = c.h[l]; P.ln_stat = c.ln_stat ? c.ln_stat[l] : nullptr;
     }
-    a.x0 = x_in[0]; a.xout = xout; a.tmq = tmq; a.ln_eps = ln_eps;
-    if (gat != nullptr) {      // the gather as the workgroups' prologue: the producer-side pieces build, a live list, p = 0.5 or eval
-        if (!(w16 != nullptr && w16_planes == 3 && D == 128 && live != nullptr)) return AMID_ERR_UNSUPPORTED;
-        AMID_CHECK_ARG(gat->table && gat->idx && gat->pos[0] && gat->pos[1] && tmq && gat->ni >= 0 && (gat->items == nullptr || gat->ni > 0));
+    a.x0 = c.x_in[0]; a.xout = c.xout; a.tmq = c.tmq; a.ln_eps = c.ln_eps;
+    const DropoutArgs drop = dropout_args(c.train, c.p_drop);
+    if (const SeqGather* gat = c.gather) {      // the gather as the workgroups' prologue: the producer-side pieces build, a live list, p = 0.5 or eval
+        if (!(pieces128 && c.live != nullptr)) return AMID_ERR_UNSUPPORTED;
+        AMID_CHECK_ARG(gat->table && gat->idx && gat->pos[0] && gat->pos[1] && c.tmq && gat->ni >= 0 && (gat->items == nullptr || gat->ni > 0));
         a.g_table = gat->table; a.g_idx = gat->idx; a.g_pos[0] = gat->pos[0]; a.g_pos[1] = gat->pos[1]; a.g_items = gat->items; a.g_ni = gat->ni;
-        a.g_scale = (train && p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
+        a.g_scale = drop.scale;
         a.g_done = gat->done;
     }
-    a.w16 = (const unsigned short*)w16; a.w16_planes = w16_planes;
-    a.one_piece = (tl_one_piece && w16 != nullptr && w16_planes == 3) ? 1 : 0;
-    a.att_scale = sqrtf(1.0f / (float)(D / H));
-    a.st = (const StepState*)step_state;
-    a.train = (train && p_drop > 0.f) ? 1 : 0;
-    a.spec = drop_spec(p_drop);
-    a.dscale = a.ffn_scale = a.train ? 1.0f / (1.0f - p_drop) : 1.0f;
+    a.w16 = (const unsigned short*)c.w16; a.w16_planes = c.w16_planes;
+    a.one_piece = (c.one_piece && c.w16 != nullptr && c.w16_planes == 3) ? 1 : 0;
+    a.att_scale = sqrtf(1.0f / (float)(D / c.H));
+    a.st = (const StepState*)c.step_state;
+    a.train = drop.train; a.spec = drop.spec; a.dscale = a.ffn_scale = drop.scale;
     SeqGeom sg;
-    sg.B = B; sg.T = T; sg.M = B * T; sg.live = live;
-    const long long bytes = 2LL * B * T * D * 4;
-    sg.act_bytes = (unsigned)bytes; sg.tm_bytes = (unsigned)(bytes / 16); sg.stats_bytes = (unsigned)(2LL * B * T * H * 8);
-    sg.save_bytes = infer ? 0u : sg.act_bytes; sg.save_stats_bytes = infer ? 0u : sg.stats_bytes;
-    if (head != nullptr) return launch_seqn_fwd(a, sg, D, 0, stream, head);       // (the default N-split build or nothing)
-    if (infer) return launch_seqn_fwd(a, sg, D, 0, stream, nullptr);             // (the default split of the pieces build or nothing)
+    sg.B = c.B; sg.T = c.T; sg.M = c.B * c.T; sg.live = c.live;
+    const long long bytes = 2LL * c.B * c.T * D * 4;
+    sg.act_bytes = (unsigned)bytes; sg.tm_bytes = (unsigned)(bytes / 16); sg.stats_bytes = (unsigned)(2LL * c.B * c.T * c.H * 8);
+    sg.save_bytes = c.infer ? 0u : sg.act_bytes; sg.save_stats_bytes = c.infer ? 0u : sg.stats_bytes;
+    if (c.head != nullptr) return launch_seqn_fwd(a, sg, D, 0, c.stream, c.head);      // (the default N-split build or nothing)
+    if (c.infer) return launch_seqn_fwd(a, sg, D, 0, c.stream, nullptr);               // (the default split of the pieces build or nothing)
     {
         int v = g_seq_fwd_variant;
         if (v == 0) v = 2;                                 // auto: the N-split build wins at every measured shape (profiles/r03_*)
-        if (w16 != nullptr && v == 1) return AMID_ERR_UNSUPPORTED;      // the whole-row build has no bf16 products
+        if (c.w16 != nullptr && v == 1) return AMID_ERR_UNSUPPORTED;      // the whole-row build has no bf16 products
         if (v != 1) {
-            int rc = launch_seqn_fwd(a, sg, D, v == 2 ? 0 : v, stream);
-            if (rc == AMID_ERR_UNSUPPORTED && w16 != nullptr) rc = launch_seqn_fwd(a, sg, D, 0, stream);
-            if (rc != AMID_ERR_UNSUPPORTED || w16 != nullptr) return rc;
+            int rc = launch_seqn_fwd(a, sg, D, v == 2 ? 0 : v, c.stream, nullptr);
+            if (rc == AMID_ERR_UNSUPPORTED && c.w16 != nullptr) rc = launch_seqn_fwd(a, sg, D, 0, c.stream, nullptr);
+            if (rc != AMID_ERR_UNSUPPORTED || c.w16 != nullptr) return rc;
         }
         if (D != 128) return AMID_ERR_UNSUPPORTED;          // the whole-row build below: D = 128 only
     }
-    const int wps = T <= 16 ? 1 : T <= 32 ? 2 : 4, spw = STRIP_WAVES / wps;
-    const int tiles = (B + spw - 1) / spw;
-    const int grid = live != nullptr ? tiles + 1 : 2 * tiles;      // the live tiles of both domains (one more when both are ragged) / every tile
-    const size_t lds = seq_lds_bytes<128>();
-    auto launch = [&](auto kern) -> int {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        kern<<<grid, STRIP_THREADS, lds, (hipStream_t)stream>>>(a, sg);
-        e = hipGetLastError();
-        return e == hipSuccess ? AMID_OK : (int)e;
-    };
-    if (wps == 1) return launch(seq_fwd_kernel<128, 1>);
-    if (wps == 2) return launch(seq_fwd_kernel<128, 2>);
-    return launch(seq_fwd_kernel<128, 4>);
+    const int wps = c.T <= 16 ? 1 : c.T <= 32 ? 2 : 4, spw = STRIP_WAVES / wps;
+    const int tiles = (c.B + spw - 1) / spw;
+    const int grid = c.live != nullptr ? tiles + 1 : 2 * tiles;      // the live tiles of both domains (one more when both are ragged) / every tile
+    if (wps == 1) return launch_lds<seq_fwd_kernel<128, 1>>(grid, STRIP_THREADS, seq_lds_bytes<128>(), c.stream, a, sg);
+    if (wps == 2) return launch_lds<seq_fwd_kernel<128, 2>>(grid, STRIP_THREADS, seq_lds_bytes<128>(), c.stream, a, sg);
+    return launch_lds<seq_fwd_kernel<128, 4>>(grid, STRIP_THREADS, seq_lds_bytes<128>(), c.stream, a, sg);
+}
+// the forwards of the folded step: seven saved tensors, three-plane images (one_piece: multiplied as single bf16 pieces), the gather in
+// front; `c` holds the entry's own parameters, the head included where it has one
+static int seq_fwd_gather(SeqFwdCall& c, const float* table, const int* idx_all, const float* pos0, const float* pos1, float* items, int NI,
+                          bool one_piece) {
+    AMID_CHECK_ARG(c.w16 != nullptr && c.ln_stat != nullptr && c.step_state);
+    const SeqGather gat{table, idx_all, {pos0, pos1}, items, NI, (StepState*)c.step_state};
+    c.w16_planes = 3; c.one_piece = one_piece; c.gather = &gat;
+    return seq_fwd_impl(c);
 }
 
 extern "C" int amid_sas_seq_fwd_f32(int n_layers, const float* const* x_in, float* xout, const float* const* ln1_w, const float* const* ln1_b,
@@ -534,8 +563,8 @@ extern "C" int amid_sas_seq_fwd_f32(int n_layers, const float* const* x_in, floa
                                     float* const* v, float* const* o, float* const* stats, float* const* r, float* const* y, float* const* h,
                                     const unsigned char* tmq, float ln_eps, int B, int T, int D, int H, const int* live,
                                     const void* step_state, int train, float p_drop, void* stream) {
-    return seq_fwd_impl(n_layers, x_in, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, qn, q, k, v, o, stats, r, y, h, tmq,
-                        ln_eps, B, T, D, H, live, step_state, train, p_drop, nullptr, stream);
+    SEQ_CALL_STEP(c); c.qn = qn; c.y = y;
+    return seq_fwd_impl(c);
 }
 
 // amid_sas_seq_fwd_split_lnstat_f32 with the train step's head (amid_head_fwd_bwd_own_vec_f32: LN_last + mean over T -- model_seq.py:385,
@@ -559,10 +588,9 @@ extern "C" int amid_sas_seq_fwd_split_lnstat_head_f32(int n_layers, const float*
                                                       void* stream) {
     AMID_CHECK_ARG(w16x3 != nullptr && ln_stat != nullptr && live != nullptr && last_ln_w != nullptr && last_ln_b != nullptr);
     HeadArgs ha;
-    if (int e = head_own_vec_args(ha, last_ln_w, last_ln_b, items, sw1, sb1, sw2, sb2, labels, domain_id, B, T, NI, D, hid, ln_eps, u, p1, p2, dp1,
-                                  dp2, loss_part, dx, ditems, ln_part, hidg)) return e;
-    return seq_fwd_impl(n_layers, x_in, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, nullptr, q, k, v, o, stats, r, nullptr,
-                        h, tmq, ln_eps, B, T, D, H, live, step_state, train, p_drop, w16x3, stream, 3, ln_stat, &ha);
+    if (int e = SEQ_HEAD_ARGS(ha)) return e;
+    SEQ_CALL_STEP(c); c.ln_stat = ln_stat; c.w16 = w16x3; c.w16_planes = 3; c.head = &ha;
+    return seq_fwd_impl(c);
 }
 
 // The same forward with the twelve projections' matrix products on v_mfma_f32_16x16x32_bf16 (operands rounded to bf16, fp32
@@ -576,8 +604,8 @@ extern "C" int amid_sas_seq_fwd_bf16w_f32(int n_layers, const float* const* x_in
                                           const unsigned char* tmq, float ln_eps, int B, int T, int D, int H, const int* live,
                                           const void* step_state, int train, float p_drop, const void* w16, void* stream) {
     AMID_CHECK_ARG(w16 != nullptr);
-    return seq_fwd_impl(n_layers, x_in, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, qn, q, k, v, o, stats, r, y, h, tmq,
-                        ln_eps, B, T, D, H, live, step_state, train, p_drop, w16, stream);
+    SEQ_CALL_STEP(c); c.qn = qn; c.y = y; c.w16 = w16;
+    return seq_fwd_impl(c);
 }
 
 // bf16 fragment images of n square [D][D] fp32 matrices (row-major [out n][in k]; transposed != 0: of their transposes):
@@ -623,8 +651,8 @@ extern "C" int amid_sas_seq_fwd_split_f32(int n_layers, const float* const* x_in
                                           const unsigned char* tmq, float ln_eps, int B, int T, int D, int H, const int* live,
                                           const void* step_state, int train, float p_drop, const void* w16x3, void* stream) {
     AMID_CHECK_ARG(w16x3 != nullptr);
-    return seq_fwd_impl(n_layers, x_in, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, qn, q, k, v, o, stats, r, y, h, tmq,
-                        ln_eps, B, T, D, H, live, step_state, train, p_drop, w16x3, stream, 3);
+    SEQ_CALL_STEP(c); c.qn = qn; c.y = y; c.w16 = w16x3; c.w16_planes = 3;
+    return seq_fwd_impl(c);
 }
 
 // amid_sas_seq_fwd_split_f32 as an INFERENCE forward (evaluation, train_sr.py:31-128: model(..., False) under no_grad): the same products
@@ -638,9 +666,8 @@ extern "C" int amid_sas_seq_fwd_split_infer_f32(int n_layers, const float* x0, f
                                                 const void* w16x3, void* stream) {
     AMID_CHECK_ARG(w16x3 != nullptr && x0 != nullptr && xout != nullptr);
     const float* xin[2] = {x0, nullptr};
-    return seq_fwd_impl(n_layers, xin, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, tmq, ln_eps, B, T, D, H, live, nullptr, 0, 0.f, w16x3, stream, 3, nullptr, nullptr,
-                        true);
+    SEQ_CALL_COMMON(c); c.x_in = xin; c.tmq = tmq; c.w16 = w16x3; c.w16_planes = 3; c.infer = true;
+    return seq_fwd_impl(c);
 }
 
 // The three forwards of the folded step / the evaluation batch with the gather K1 as their workgroups' PROLOGUE (round 6): layer 0's input
@@ -661,13 +688,11 @@ extern "C" int amid_sas_seq_fwd_gather_head_f32(int n_layers, const float* const
                                                 const long long* domain_id, int NI, int hid, float* u, float* p1, float* p2, float* dp1,
                                                 float* dp2, float* loss_part, float* dx, float* ditems, float* ln_part, float* hidg,
                                                 const float* table, const int* idx_all, const float* pos0, const float* pos1, void* stream) {
-    AMID_CHECK_ARG(w16x3 != nullptr && ln_stat != nullptr && live != nullptr && last_ln_w != nullptr && last_ln_b != nullptr && step_state);
+    AMID_CHECK_ARG(live != nullptr && last_ln_w != nullptr && last_ln_b != nullptr);
     HeadArgs ha;
-    if (int e = head_own_vec_args(ha, last_ln_w, last_ln_b, items, sw1, sb1, sw2, sb2, labels, domain_id, B, T, NI, D, hid, ln_eps, u, p1, p2, dp1,
-                                  dp2, loss_part, dx, ditems, ln_part, hidg)) return e;
-    const SeqGather gat{table, idx_all, {pos0, pos1}, items, NI, (StepState*)step_state};
-    return seq_fwd_impl(n_layers, x_in, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, nullptr, q, k, v, o, stats, r, nullptr,
-                        h, tmq, ln_eps, B, T, D, H, live, step_state, train, p_drop, w16x3, stream, 3, ln_stat, &ha, false, &gat);
+    if (int e = SEQ_HEAD_ARGS(ha)) return e;
+    SEQ_CALL_STEP(c); c.ln_stat = ln_stat; c.w16 = w16x3; c.head = &ha;
+    return seq_fwd_gather(c, table, idx_all, pos0, pos1, items, NI, false);
 }
 extern "C" int amid_sas_seq_fwd_gather_f32(int n_layers, const float* const* x_in, float* xout, const float* const* ln1_w,
                                            const float* const* ln1_b, const float* const* w_in, const float* const* b_in,
@@ -678,10 +703,8 @@ extern "C" int amid_sas_seq_fwd_gather_f32(int n_layers, const float* const* x_i
                                            float* const* h, unsigned char* tmq, float ln_eps, int B, int T, int D, int H,
                                            const int* live, void* step_state, int train, float p_drop, const void* w16x3, float* items, int NI,
                                            const float* table, const int* idx_all, const float* pos0, const float* pos1, void* stream) {
-    AMID_CHECK_ARG(w16x3 != nullptr && ln_stat != nullptr && step_state);
-    const SeqGather gat{table, idx_all, {pos0, pos1}, items, NI, (StepState*)step_state};
-    return seq_fwd_impl(n_layers, x_in, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, nullptr, q, k, v, o, stats, r, nullptr, h,
-                        tmq, ln_eps, B, T, D, H, live, step_state, train, p_drop, w16x3, stream, 3, ln_stat, nullptr, false, &gat);
+    SEQ_CALL_STEP(c); c.ln_stat = ln_stat; c.w16 = w16x3;
+    return seq_fwd_gather(c, table, idx_all, pos0, pos1, items, NI, false);
 }
 // amid_sas_seq_fwd_gather_head_f32 / amid_sas_seq_fwd_gather_f32 with the twelve projection products on ONE bf16 piece per operand (compute = "bf16"
 // on the folded step, round 6): the same launches -- three-plane images, pieces in the exchange (the LayerNorm statistics still see the exact
@@ -699,13 +722,11 @@ extern "C" int amid_sas_seq_fwd_gather_head_p1_f32(int n_layers, const float* co
                                                    const long long* domain_id, int NI, int hid, float* u, float* p1, float* p2, float* dp1,
                                                    float* dp2, float* loss_part, float* dx, float* ditems, float* ln_part, float* hidg,
                                                    const float* table, const int* idx_all, const float* pos0, const float* pos1, void* stream) {
-    tl_one_piece = 1;
-    const int rc = amid_sas_seq_fwd_gather_head_f32(n_layers, x_in, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, ln_stat, q, k, v, o,
-                                                    stats, r, h, tmq, ln_eps, B, T, D, H, live, step_state, train, p_drop, w16x3, last_ln_w, last_ln_b, items,
-                                                    sw1, sb1, sw2, sb2, labels, domain_id, NI, hid, u, p1, p2, dp1, dp2, loss_part, dx, ditems, ln_part, hidg,
-                                                    table, idx_all, pos0, pos1, stream);
-    tl_one_piece = 0;
-    return rc;
+    AMID_CHECK_ARG(live != nullptr && last_ln_w != nullptr && last_ln_b != nullptr);
+    HeadArgs ha;
+    if (int e = SEQ_HEAD_ARGS(ha)) return e;
+    SEQ_CALL_STEP(c); c.ln_stat = ln_stat; c.w16 = w16x3; c.head = &ha;
+    return seq_fwd_gather(c, table, idx_all, pos0, pos1, items, NI, true);
 }
 extern "C" int amid_sas_seq_fwd_gather_p1_f32(int n_layers, const float* const* x_in, float* xout, const float* const* ln1_w,
                                               const float* const* ln1_b, const float* const* w_in, const float* const* b_in,
@@ -716,11 +737,8 @@ extern "C" int amid_sas_seq_fwd_gather_p1_f32(int n_layers, const float* const* 
                                               float* const* h, unsigned char* tmq, float ln_eps, int B, int T, int D, int H,
                                               const int* live, void* step_state, int train, float p_drop, const void* w16x3, float* items, int NI,
                                               const float* table, const int* idx_all, const float* pos0, const float* pos1, void* stream) {
-    tl_one_piece = 1;
-    const int rc = amid_sas_seq_fwd_gather_f32(n_layers, x_in, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, ln_stat, q, k, v, o, stats, r,
-                                               h, tmq, ln_eps, B, T, D, H, live, step_state, train, p_drop, w16x3, items, NI, table, idx_all, pos0, pos1, stream);
-    tl_one_piece = 0;
-    return rc;
+    SEQ_CALL_STEP(c); c.ln_stat = ln_stat; c.w16 = w16x3;
+    return seq_fwd_gather(c, table, idx_all, pos0, pos1, items, NI, true);
 }
 extern "C" int amid_sas_seq_fwd_gather_infer_f32(int n_layers, float* xout, const float* const* ln1_w, const float* const* ln1_b,
                                                  const float* const* w_in, const float* const* b_in, const float* const* w_o,
@@ -732,9 +750,8 @@ extern "C" int amid_sas_seq_fwd_gather_infer_f32(int n_layers, float* xout, cons
     // (nothing is stored but xout: x_in[0] and the mask bytes are only names here -- the mask word stays in registers)
     const float* xin[2] = {xout, nullptr};
     const SeqGather gat{table, idx_all, {pos0, pos1}, nullptr, 0, nullptr};
-    return seq_fwd_impl(n_layers, xin, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, (const unsigned char*)xout, ln_eps, B, T, D, H, live, nullptr, 0, 0.f, w16x3, stream, 3,
-                        nullptr, nullptr, true, &gat);
+    SEQ_CALL_COMMON(c); c.x_in = xin; c.tmq = (const unsigned char*)xout; c.w16 = w16x3; c.w16_planes = 3; c.infer = true; c.gather = &gat;
+    return seq_fwd_impl(c);
 }
 
 // amid_sas_seq_fwd_split_f32 that saves SEVEN tensors per layer instead of nine: qn = LN1(x) and y = LN2(r) are not stored; ln_stat[l]
@@ -750,6 +767,9 @@ extern "C" int amid_sas_seq_fwd_split_lnstat_f32(int n_layers, const float* cons
                                                  const int* live, const void* step_state, int train, float p_drop, const void* w16x3,
                                                  void* stream) {
     AMID_CHECK_ARG(w16x3 != nullptr && ln_stat != nullptr);
-    return seq_fwd_impl(n_layers, x_in, xout, ln1_w, ln1_b, w_in, b_in, w_o, b_o, ln2_w, ln2_b, w1, b1, w2, b2, nullptr, q, k, v, o, stats, r, nullptr, h,
-                        tmq, ln_eps, B, T, D, H, live, step_state, train, p_drop, w16x3, stream, 3, ln_stat);
+    SEQ_CALL_STEP(c); c.ln_stat = ln_stat; c.w16 = w16x3; c.w16_planes = 3;
+    return seq_fwd_impl(c);
 }
+#undef SEQ_HEAD_ARGS
+#undef SEQ_CALL_STEP
+#undef SEQ_CALL_COMMON

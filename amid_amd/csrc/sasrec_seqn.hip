@@ -748,51 +748,29 @@ __global__ __launch_bounds__(64 * WPS * NS) void seqn_fwd_px_head_kernel(const S
 }
 
 template <int D, int WPS, int NS>
-static int seqn_launch_px(const SeqFwdArgs& a, const SeqGeom& sg, void* stream, const HeadArgs* head = nullptr) {
+static int seqn_launch_px(const SeqFwdArgs& a, const SeqGeom& sg, void* stream, const HeadArgs* head) {
     constexpr size_t lds = (size_t)(3 * (D * D / 2) + WPS * XpStrip<D>::FLOATS + 2 * WPS * NS * 16) * sizeof(float);
+    constexpr int block = 64 * WPS * NS;
+    // the builds a folded step asks for (T 33 ... 64; 17 ... 32, round 6): only they carry the head on the tail and the one-piece products
+    constexpr bool FOLDED = (WPS == 4 && NS == 2) || (WPS == 2 && NS == 4);
     const int grid = sg.live != nullptr ? sg.B : 2 * sg.B;
     if (head != nullptr) {
-        if constexpr ((WPS == 4 && NS == 2) || (WPS == 2 && NS == 4)) {      // (the builds launch_seqn_fwd asks the head for: T 33 ... 64; 17 ... 32, round 6)
+        if constexpr (FOLDED) {
             // (the head's carve inside the three plane slots, its rows T <= 16 HEAD_CHUNK / 2, a workgroup per LIVE sequence = per sample)
             if (sg.live == nullptr || head_lds_floats(D, head->hid) > (size_t)3 * (D * D / 2) || sg.T > 16 * (HEAD_CHUNK / 2) || head->D != D ||
                 head->B != sg.B || head->T != sg.T)
                 return AMID_ERR_UNSUPPORTED;
-            if (a.one_piece) {
-                auto kern1 = seqn_fwd_px_head_kernel<D, WPS, NS, true>;
-                static unsigned long long attr_done1 = 0;
-                if (int rc = lds_attr_once((const void*)kern1, lds, attr_done1)) return rc;
-                kern1<<<grid, 64 * WPS * NS, lds, (hipStream_t)stream>>>(a, sg, *head);
-                hipError_t e1 = hipGetLastError();
-                return e1 == hipSuccess ? AMID_OK : (int)e1;
-            }
-            auto kern = seqn_fwd_px_head_kernel<D, WPS, NS>;
-            static unsigned long long attr_done = 0;
-            if (int rc = lds_attr_once((const void*)kern, lds, attr_done)) return rc;
-            kern<<<grid, 64 * WPS * NS, lds, (hipStream_t)stream>>>(a, sg, *head);
-            hipError_t e = hipGetLastError();
-            return e == hipSuccess ? AMID_OK : (int)e;
+            return a.one_piece ? launch_lds<seqn_fwd_px_head_kernel<D, WPS, NS, true>>(grid, block, lds, stream, a, sg, *head)
+                               : launch_lds<seqn_fwd_px_head_kernel<D, WPS, NS>>(grid, block, lds, stream, a, sg, *head);
         } else {
             return AMID_ERR_UNSUPPORTED;
         }
     }
     if (a.one_piece) {
-        if constexpr ((WPS == 4 && NS == 2) || (WPS == 2 && NS == 4)) {      // (the builds a folded step asks for)
-            auto kern1 = seqn_fwd_px_kernel<D, WPS, NS, true>;
-            static unsigned long long attr_done1 = 0;
-            if (int rc = lds_attr_once((const void*)kern1, lds, attr_done1)) return rc;
-            kern1<<<grid, 64 * WPS * NS, lds, (hipStream_t)stream>>>(a, sg);
-            hipError_t e1 = hipGetLastError();
-            return e1 == hipSuccess ? AMID_OK : (int)e1;
-        } else {
-            return AMID_ERR_UNSUPPORTED;
-        }
+        if constexpr (FOLDED) return launch_lds<seqn_fwd_px_kernel<D, WPS, NS, true>>(grid, block, lds, stream, a, sg);
+        else return AMID_ERR_UNSUPPORTED;
     }
-    auto kern = seqn_fwd_px_kernel<D, WPS, NS>;
-    static unsigned long long attr_done = 0;
-    if (int rc = lds_attr_once((const void*)kern, lds, attr_done)) return rc;
-    kern<<<grid, 64 * WPS * NS, lds, (hipStream_t)stream>>>(a, sg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AMID_OK : (int)e;
+    return launch_lds<seqn_fwd_px_kernel<D, WPS, NS>>(grid, block, lds, stream, a, sg);
 }
 
 template <int D, int WPS, bool BF, bool P3 = false> static constexpr size_t seqn_lds_bytes() {
@@ -801,18 +779,11 @@ template <int D, int WPS, bool BF, bool P3 = false> static constexpr size_t seqn
 
 template <int D, int WPS, int NS, bool BF, bool P3 = false>
 static int seqn_launch_t(const SeqFwdArgs& a, const SeqGeom& sg, void* stream) {
-    constexpr size_t lds = seqn_lds_bytes<D, WPS, BF, P3>();
-    auto kern = seqn_fwd_kernel<D, WPS, NS, BF, P3>;
-    static unsigned long long attr_done = 0;          // per device (common.h lds_attr_once): the same scheme as the backward's launcher
-    if (int rc = lds_attr_once((const void*)kern, lds, attr_done)) return rc;
-    const int grid = sg.live != nullptr ? sg.B : 2 * sg.B;
-    kern<<<grid, 64 * WPS * NS, lds, (hipStream_t)stream>>>(a, sg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AMID_OK : (int)e;
+    return launch_lds<seqn_fwd_kernel<D, WPS, NS, BF, P3>>(sg.live != nullptr ? sg.B : 2 * sg.B, 64 * WPS * NS, seqn_lds_bytes<D, WPS, BF, P3>(), stream, a, sg);
 }
 
 template <int WPS, int NS>
-static int seqn_launch(const SeqFwdArgs& a, const SeqGeom& sg, void* stream, const HeadArgs* head = nullptr) {
+static int seqn_launch(const SeqFwdArgs& a, const SeqGeom& sg, void* stream, const HeadArgs* head) {
     if (head != nullptr) {        // the head rides on the producer-side pieces build only
         if constexpr ((128 / 16 / NS) % 2 == 0) { if (a.w16 != nullptr && a.w16_planes == 3) return seqn_launch_px<128, WPS, NS>(a, sg, stream, head); }
         return AMID_ERR_UNSUPPORTED;
@@ -820,7 +791,7 @@ static int seqn_launch(const SeqFwdArgs& a, const SeqGeom& sg, void* stream, con
     if (a.w16 != nullptr && a.w16_planes == 3) {
         // the producer-side pieces build (seqn_fwd_px_kernel) wherever a wave owns whole k-steps (an even number of column tiles);
         // SeqRing16x3's build -- every wave splits its strip's whole row itself -- for the one-tile parts of the diagnostic variant 18
-        if constexpr ((128 / 16 / NS) % 2 == 0) return seqn_launch_px<128, WPS, NS>(a, sg, stream);
+        if constexpr ((128 / 16 / NS) % 2 == 0) return seqn_launch_px<128, WPS, NS>(a, sg, stream, nullptr);
         else return seqn_launch_t<128, WPS, NS, true, true>(a, sg, stream);
     }
     return a.w16 != nullptr ? seqn_launch_t<128, WPS, NS, true>(a, sg, stream) : seqn_launch_t<128, WPS, NS, false>(a, sg, stream);
@@ -848,11 +819,11 @@ int launch_seqn_fwd(const SeqFwdArgs& a, const SeqGeom& sg, int D, int variant, 
     if (variant == 0) variant = wps == 4 ? 42 : wps == 2 ? 24 : 14;
     if (variant / 10 != wps) return AMID_ERR_UNSUPPORTED;
     switch (variant) {
-        case 42: return seqn_launch<4, 2>(a, sg, stream);
-        case 22: return seqn_launch<2, 2>(a, sg, stream);
-        case 24: return seqn_launch<2, 4>(a, sg, stream);
-        case 14: return seqn_launch<1, 4>(a, sg, stream);
-        case 18: return seqn_launch<1, 8>(a, sg, stream);
+        case 42: return seqn_launch<4, 2>(a, sg, stream, nullptr);
+        case 22: return seqn_launch<2, 2>(a, sg, stream, nullptr);
+        case 24: return seqn_launch<2, 4>(a, sg, stream, nullptr);
+        case 14: return seqn_launch<1, 4>(a, sg, stream, nullptr);
+        case 18: return seqn_launch<1, 8>(a, sg, stream, nullptr);
         default: return AMID_ERR_UNSUPPORTED;
     }
 }

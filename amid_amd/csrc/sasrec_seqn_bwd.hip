@@ -395,13 +395,7 @@ template <int D, int WPS, bool BF> static constexpr size_t seqn_bwd_lds_bytes() 
 
 template <int D, int WPS, int NS, bool BF>
 static int seqn_bwd_launch_t(const SeqBwdArgs& a, const StripGeom& sg, void* stream) {
-    constexpr size_t lds = seqn_bwd_lds_bytes<D, WPS, BF>();
-    auto kern = seqn_bwd_kernel<D, WPS, NS, BF>;
-    static unsigned long long attr_done = 0;          // per device, as the strip launches (common.h lds_attr_once)
-    if (int rc = lds_attr_once((const void*)kern, lds, attr_done)) return rc;
-    kern<<<sg.B, 512, lds, (hipStream_t)stream>>>(a, sg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AMID_OK : (int)e;
+    return launch_lds<seqn_bwd_kernel<D, WPS, NS, BF>>(sg.B, 512, seqn_bwd_lds_bytes<D, WPS, BF>(), stream, a, sg);
 }
 
 // D = 64 (8 heads of 8 dims): four column tiles -- two parts at four strips, four at two, eight waves either way; fp32 products only

@@ -564,24 +564,10 @@ static int make_rider(SortRider& rd, const void* sort_plan, int sort_phase) {
 // a strip launch with a sort rider: rd.plan.nblk extra workgroups in front of the tiles'
 // (extra: further rider workgroups behind the sort's -- the scorer sums of strip_qkv_bwd_kernel)
 template <auto KERNEL, int DVAL, class... Args>
-static int launch_strip_rider_x(const StripGeom& sg, const SortRider& rd, int extra, void* stream, const Args&... args) {
-    static unsigned long long attr_done = 0;
+static int launch_strip_rider(const StripGeom& sg, const SortRider& rd, int extra, void* stream, const Args&... args) {
     // (the rider workgroups run their sort phase on the head of the dynamic LDS: the 4 096-bin scatter needs 48 KB)
     if (rd.phase != 0 && strip_lds_bytes<DVAL>() < (rd.plan.g0.bits > 10 ? sizeof(SortScatterLds<OS_BINS_MAX>) : sizeof(SortScatterLds<1024>))) return AMID_ERR_UNSUPPORTED;
-    if (int rc = lds_attr_once((const void*)KERNEL, strip_lds_bytes<DVAL>(), attr_done)) return rc;
-    KERNEL<<<2 * sg.tpg + rider_blocks_host(rd) + extra, STRIP_THREADS, strip_lds_bytes<DVAL>(), (hipStream_t)stream>>>(args..., sg, rd);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AMID_OK : (int)e;
-}
-template <auto KERNEL, int DVAL, class... Args>
-static int launch_strip_rider(const StripGeom& sg, const SortRider& rd, void* stream, const Args&... args) {
-    static unsigned long long attr_done = 0;
-    // (the rider workgroups run their sort phase on the head of the dynamic LDS: the 4 096-bin scatter needs 48 KB)
-    if (rd.phase != 0 && strip_lds_bytes<DVAL>() < (rd.plan.g0.bits > 10 ? sizeof(SortScatterLds<OS_BINS_MAX>) : sizeof(SortScatterLds<1024>))) return AMID_ERR_UNSUPPORTED;
-    if (int rc = lds_attr_once((const void*)KERNEL, strip_lds_bytes<DVAL>(), attr_done)) return rc;
-    KERNEL<<<2 * sg.tpg + rider_blocks_host(rd), STRIP_THREADS, strip_lds_bytes<DVAL>(), (hipStream_t)stream>>>(args..., sg, rd);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AMID_OK : (int)e;
+    return launch_lds<KERNEL>(2 * sg.tpg + rider_blocks_host(rd) + extra, STRIP_THREADS, strip_lds_bytes<DVAL>(), stream, args..., sg, rd);
 }
 
 extern "C" int amid_sas_strip_tile_rows(void) { return STRIP_TILE; }
@@ -592,17 +578,72 @@ extern "C" int amid_strip_stamps_read(unsigned long long* host) {       // diagn
 }
 #endif
 
+// the one fill of a layer's LayerNorm 1 + q / k / v arguments: the training and the inference entries, and the block a fused predecessor
+// carries for the next layer (x: the rows it reads or, fused, stores as the saved layer input; NULL: neither)
+static void fill_strip_qkv(StripQkvArgs& a, const float* x, const float* const* ln_w, const float* const* ln_b, const float* const* w_in,
+                           const float* const* b_in, float ln_eps, float* qn, float* q, float* k, float* v) {
+    a.x = x; a.qn = qn; a.q = q; a.k = k; a.v = v; a.ln_eps = ln_eps;
+    for (int g = 0; g < 2; ++g) { a.ln_w[g] = ln_w[g]; a.ln_b[g] = ln_b[g]; a.w_in[g] = w_in[g]; a.b_in[g] = b_in[g]; }
+}
+
 extern "C" int amid_sas_strip_qkv_fwd_f32(const float* x, const float* const* ln_w, const float* const* ln_b, const float* const* w_in,
                                           const float* const* b_in, float ln_eps, int B, int T, int D, const int* live, float* qn, float* q,
                                           float* k, float* v, void* stream) {
     AMID_CHECK_ARG(x && ln_w && ln_b && w_in && b_in && qn && q && k && v);
     StripQkvArgs a;
-    a.x = x; a.qn = qn; a.q = q; a.k = k; a.v = v; a.ln_eps = ln_eps;
-    for (int g = 0; g < 2; ++g) { a.ln_w[g] = ln_w[g]; a.ln_b[g] = ln_b[g]; a.w_in[g] = w_in[g]; a.b_in[g] = b_in[g]; }
+    fill_strip_qkv(a, x, ln_w, ln_b, w_in, b_in, ln_eps, qn, q, k, v);
     StripGeom sg;
     if (int e = make_strip_geom(B, T, D, live, &sg)) return e;
     if (D == 128) return launch_strip<strip_qkv_fwd_kernel<128>, 128>(sg, stream, a);
     if (D == 64) return launch_strip<strip_qkv_fwd_kernel<64>, 64>(sg, stream, a);
+    return AMID_ERR_UNSUPPORTED;
+}
+
+// out-projection + feed-forward of a layer as its two entries state it (every field null / zero unless named).  The optional block: the next
+// layer's LayerNorm 1 + q / k / v on the output in the same launch (absent: nln_w == NULL).  save = false: the inference form -- r, y, h and
+// the next layer's input are not stored, no dropout site draws.
+struct StripOffCall {
+    const float* o = nullptr; const float* qn = nullptr;
+    FamC w_o = nullptr, b_o = nullptr, ln_w = nullptr, ln_b = nullptr, w1 = nullptr, b1 = nullptr, w2 = nullptr, b2 = nullptr;
+    const unsigned char* tmq = nullptr; float ln_eps = 0.f;
+    int B = 0, T = 0, D = 0; const int* live = nullptr; void* stream = nullptr;
+    int layer = 0; const void* step_state = nullptr; int train = 0; float p_drop = 0.f;
+    float* r = nullptr; float* y = nullptr; float* h = nullptr; float* xo = nullptr;
+    FamC nln_w = nullptr, nln_b = nullptr, nw_in = nullptr, nb_in = nullptr;
+    float* nqn = nullptr; float* nq = nullptr; float* nk = nullptr; float* nv = nullptr;
+    bool save = true;
+    bool next() const { return nln_w != nullptr; }
+    bool next_operands() const { return nln_b && nw_in && nb_in && nqn && nq && nk && nv; }
+};
+// a record `c` with the parameters both entries take bound to its fields of the same names
+#define STRIP_OFF_CALL(c)                                                                                                                       \
+    StripOffCall c;                                                                                                                             \
+    c.o = o; c.qn = qn; c.w_o = w_o; c.b_o = b_o; c.ln_w = ln_w; c.ln_b = ln_b; c.w1 = w1; c.b1 = b1; c.w2 = w2; c.b2 = b2; c.tmq = tmq;             \
+    c.ln_eps = ln_eps; c.B = B; c.T = T; c.D = D; c.live = live; c.stream = stream; c.xo = xo; c.nln_w = nln_w; c.nln_b = nln_b; c.nw_in = nw_in;   \
+    c.nb_in = nb_in; c.nqn = nqn; c.nq = nq; c.nk = nk; c.nv = nv
+
+template <int D, bool SAVE>
+static int launch_oproj_ffn_fwd(const StripGeom& sg, void* stream, bool next, const StripOffArgs& a, const StripQkvArgs& nx) {
+    return next ? launch_strip<strip_oproj_ffn_fwd_kernel<D, true, SAVE>, D>(sg, stream, a, nx)
+                : launch_strip<strip_oproj_ffn_fwd_kernel<D, false, SAVE>, D>(sg, stream, a, nx);
+}
+static int strip_oproj_ffn_fwd(const StripOffCall& c) {
+    const bool next = c.next();
+    StripOffArgs a;
+    a.o = c.o; a.qn = c.qn; a.tmq = c.tmq; a.r = c.r; a.y = c.y; a.h = c.h; a.xo = c.xo; a.ln_eps = c.ln_eps;
+    a.st = (const StepState*)c.step_state; a.layer = c.layer;
+    const DropoutArgs d = dropout_args(c.train, c.p_drop);
+    a.train = d.train; a.spec = d.spec; a.scale = d.scale;
+    for (int g = 0; g < 2; ++g) {
+        a.w_o[g] = c.w_o[g]; a.b_o[g] = c.b_o[g]; a.ln_w[g] = c.ln_w[g]; a.ln_b[g] = c.ln_b[g];
+        a.w1[g] = c.w1[g]; a.b1[g] = c.b1[g]; a.w2[g] = c.w2[g]; a.b2[g] = c.b2[g];
+    }
+    StripQkvArgs nx = {};
+    if (next) fill_strip_qkv(nx, c.save ? c.xo : nullptr, c.nln_w, c.nln_b, c.nw_in, c.nb_in, c.ln_eps, c.nqn, c.nq, c.nk, c.nv);
+    StripGeom sg;
+    if (int e = make_strip_geom(c.B, c.T, c.D, c.live, &sg)) return e;
+    if (c.D == 128) return c.save ? launch_oproj_ffn_fwd<128, true>(sg, c.stream, next, a, nx) : launch_oproj_ffn_fwd<128, false>(sg, c.stream, next, a, nx);
+    if (c.D == 64) return c.save ? launch_oproj_ffn_fwd<64, true>(sg, c.stream, next, a, nx) : launch_oproj_ffn_fwd<64, false>(sg, c.stream, next, a, nx);
     return AMID_ERR_UNSUPPORTED;
 }
 
@@ -613,29 +654,10 @@ extern "C" int amid_sas_strip_oproj_ffn_fwd_f32(const float* o, const float* qn,
                                                 const void* step_state, int train, float p_drop, float* r, float* y, float* h, float* xo,
                                                 const float* const* nln_w, const float* const* nln_b, const float* const* nw_in,
                                                 const float* const* nb_in, float* nqn, float* nq, float* nk, float* nv, void* stream) {
+    STRIP_OFF_CALL(c); c.layer = layer; c.step_state = step_state; c.train = train; c.p_drop = p_drop; c.r = r; c.y = y; c.h = h;
     AMID_CHECK_ARG(o && qn && w_o && b_o && ln_w && ln_b && w1 && b1 && w2 && b2 && r && y && h && xo && (!train || step_state));
-    const bool next = nln_w != nullptr;
-    AMID_CHECK_ARG(!next || (nln_b && nw_in && nb_in && nqn && nq && nk && nv));
-    StripOffArgs a;
-    a.o = o; a.qn = qn; a.tmq = tmq; a.r = r; a.y = y; a.h = h; a.xo = xo; a.ln_eps = ln_eps;
-    a.st = (const StepState*)step_state; a.layer = layer;
-    a.train = (train && p_drop > 0.f) ? 1 : 0;
-    a.spec = drop_spec(p_drop);
-    a.scale = a.train ? 1.0f / (1.0f - p_drop) : 1.0f;
-    StripQkvArgs nx = {};
-    for (int g = 0; g < 2; ++g) {
-        a.w_o[g] = w_o[g]; a.b_o[g] = b_o[g]; a.ln_w[g] = ln_w[g]; a.ln_b[g] = ln_b[g];
-        a.w1[g] = w1[g]; a.b1[g] = b1[g]; a.w2[g] = w2[g]; a.b2[g] = b2[g];
-        if (next) { nx.ln_w[g] = nln_w[g]; nx.ln_b[g] = nln_b[g]; nx.w_in[g] = nw_in[g]; nx.b_in[g] = nb_in[g]; }
-    }
-    if (next) { nx.x = xo; nx.qn = nqn; nx.q = nq; nx.k = nk; nx.v = nv; nx.ln_eps = ln_eps; }
-    StripGeom sg;
-    if (int e = make_strip_geom(B, T, D, live, &sg)) return e;
-    if (D == 128 && next) return launch_strip<strip_oproj_ffn_fwd_kernel<128, true>, 128>(sg, stream, a, nx);
-    if (D == 128) return launch_strip<strip_oproj_ffn_fwd_kernel<128, false>, 128>(sg, stream, a, nx);
-    if (D == 64 && next) return launch_strip<strip_oproj_ffn_fwd_kernel<64, true>, 64>(sg, stream, a, nx);
-    if (D == 64) return launch_strip<strip_oproj_ffn_fwd_kernel<64, false>, 64>(sg, stream, a, nx);
-    return AMID_ERR_UNSUPPORTED;
+    AMID_CHECK_ARG(!c.next() || c.next_operands());
+    return strip_oproj_ffn_fwd(c);
 }
 
 // ---- the evaluation batch's strip launches (inference forms; SasrecEngine._enqueue_eval_encoders beyond 64 tokens) ----
@@ -649,8 +671,7 @@ extern "C" int amid_sas_strip_qkv_fwd_gather_infer_f32(const float* table, const
     for (int g = 0; g < 2; ++g) AMID_CHECK_ARG(ln_w[g] && ln_b[g] && w_in[g] && b_in[g]);
     if (!amid_sas_strip_infer_supported(T, D)) return AMID_ERR_UNSUPPORTED;
     StripQkvArgs a;
-    a.x = nullptr; a.qn = qn; a.q = q; a.k = k; a.v = v; a.ln_eps = ln_eps;
-    for (int g = 0; g < 2; ++g) { a.ln_w[g] = ln_w[g]; a.ln_b[g] = ln_b[g]; a.w_in[g] = w_in[g]; a.b_in[g] = b_in[g]; }
+    fill_strip_qkv(a, nullptr, ln_w, ln_b, w_in, b_in, ln_eps, qn, q, k, v);
     StripGatherArgs ga;
     ga.table = table; ga.idx = idx_all; ga.pos[0] = pos0; ga.pos[1] = pos1; ga.tmq = tmq;
     StripGeom sg;
@@ -665,66 +686,50 @@ extern "C" int amid_sas_strip_oproj_ffn_fwd_infer_f32(const float* o, const floa
                                                       const unsigned char* tmq, float ln_eps, int B, int T, int D, const int* live, float* xo,
                                                       const float* const* nln_w, const float* const* nln_b, const float* const* nw_in,
                                                       const float* const* nb_in, float* nqn, float* nq, float* nk, float* nv, void* stream) {
+    STRIP_OFF_CALL(c); c.save = false;
     AMID_CHECK_ARG(o && qn && w_o && b_o && ln_w && ln_b && w1 && b1 && w2 && b2 && B > 0 && T > 0 && D > 0);
-    const bool next = nln_w != nullptr;
-    AMID_CHECK_ARG(next ? (nln_b && nw_in && nb_in && nqn && nq && nk && nv) : xo != nullptr);
+    AMID_CHECK_ARG(c.next() ? c.next_operands() : xo != nullptr);
     for (int g = 0; g < 2; ++g) {
         AMID_CHECK_ARG(w_o[g] && b_o[g] && ln_w[g] && ln_b[g] && w1[g] && b1[g] && w2[g] && b2[g]);
-        AMID_CHECK_ARG(!next || (nln_w[g] && nln_b[g] && nw_in[g] && nb_in[g]));
+        AMID_CHECK_ARG(!c.next() || (nln_w[g] && nln_b[g] && nw_in[g] && nb_in[g]));
     }
     if (!amid_sas_strip_infer_supported(T, D)) return AMID_ERR_UNSUPPORTED;
-    StripOffArgs a;
-    a.o = o; a.qn = qn; a.tmq = tmq; a.r = nullptr; a.y = nullptr; a.h = nullptr; a.xo = xo; a.ln_eps = ln_eps;
-    a.st = nullptr; a.layer = 0; a.train = 0; a.spec = drop_spec(0.f); a.scale = 1.0f;
-    StripQkvArgs nx = {};
-    for (int g = 0; g < 2; ++g) {
-        a.w_o[g] = w_o[g]; a.b_o[g] = b_o[g]; a.ln_w[g] = ln_w[g]; a.ln_b[g] = ln_b[g];
-        a.w1[g] = w1[g]; a.b1[g] = b1[g]; a.w2[g] = w2[g]; a.b2[g] = b2[g];
-        if (next) { nx.ln_w[g] = nln_w[g]; nx.ln_b[g] = nln_b[g]; nx.w_in[g] = nw_in[g]; nx.b_in[g] = nb_in[g]; }
-    }
-    if (next) { nx.x = nullptr; nx.qn = nqn; nx.q = nq; nx.k = nk; nx.v = nv; nx.ln_eps = ln_eps; }
-    StripGeom sg;
-    if (int e = make_strip_geom(B, T, D, live, &sg)) return e;
-    if (D == 128 && next) return launch_strip<strip_oproj_ffn_fwd_kernel<128, true, false>, 128>(sg, stream, a, nx);
-    if (D == 128) return launch_strip<strip_oproj_ffn_fwd_kernel<128, false, false>, 128>(sg, stream, a, nx);
-    if (next) return launch_strip<strip_oproj_ffn_fwd_kernel<64, true, false>, 64>(sg, stream, a, nx);
-    return launch_strip<strip_oproj_ffn_fwd_kernel<64, false, false>, 64>(sg, stream, a, nx);
+    return strip_oproj_ffn_fwd(c);
 }
+#undef STRIP_OFF_CALL
 
-static void fill_ffn_bwd(StripFfnBwdArgs& a, const float* dxo, const unsigned char* tmq, const float* h, const float* r,
-                         const float* const* ln_w, const float* const* w1T, const float* const* w2T, const float* const* woT, float ln_eps,
-                         int layer, const void* step_state, int train, float p_drop, float* dpre2, float* dpre1, float* dr, float* d_o,
-                         float* ln_part) {
-    a.dxo = dxo; a.tmq = tmq; a.h = h; a.r = r; a.dpre2 = dpre2; a.dpre1 = dpre1; a.dr = dr; a.d_o = d_o; a.ln_part = ln_part;
-    a.ln_eps = ln_eps; a.st = (const StepState*)step_state; a.layer = layer;
-    a.train = (train && p_drop > 0.f) ? 1 : 0;
-    a.spec = drop_spec(p_drop);
-    a.scale = a.train ? 1.0f / (1.0f - p_drop) : 1.0f;
-    for (int g = 0; g < 2; ++g) { a.ln_w[g] = ln_w[g]; a.w1T[g] = w1T[g]; a.w2T[g] = w2T[g]; a.woT[g] = woT[g]; }
+// what rides on a backward strip launch and where it goes (every field null / zero unless named; a rider is absent with sort_plan == NULL:
+// phase `sort_phase` (1 .. 4) of a sort plan -- amid_sort_plan_pack -- as extra workgroups in front of the tiles')
+struct StripBwdLaunch {
+    int B = 0, T = 0, D = 0; const int* live = nullptr;
+    const void* sort_plan = nullptr; int sort_phase = 0;
+    int mma_bf16 = 0;                    // 0: fp32 products, 1: operands rounded to bf16, 3: three bf16 pieces (D 128)
+    void* stream = nullptr;
+};
+#define STRIP_BWD_LAUNCH(l) StripBwdLaunch l; l.B = B; l.T = T; l.D = D; l.live = live; l.mma_bf16 = mma_bf16; l.stream = stream
+#define STRIP_BWD_RIDER(l) l.sort_plan = sort_plan; l.sort_phase = sort_phase
+
+// (BF: the products -- 0 fp32, 1 operands rounded to bf16, 3 three bf16 pieces; the build with the rider's phase or the one without)
+template <int D, int BF>
+static int launch_ffn_bwd(const StripGeom& sg, const SortRider& rd, void* stream, const StripFfnBwdArgs& a) {
+    return rd.phase ? launch_strip_rider<strip_ffn_bwd_kernel<D, 2, BF>, D>(sg, rd, 0, stream, a)
+                    : launch_strip_rider<strip_ffn_bwd_kernel<D, 0, BF>, D>(sg, rd, 0, stream, a);
 }
-
 // ln_part: [2 * ceil(B T / amid_sas_strip_tile_rows())][2][D]; domain g's partial sums are slots [g * tpg, (g + 1) * tpg)
-static int strip_ffn_bwd(const float* dxo, const unsigned char* tmq, const float* h, const float* r, const float* const* ln_w,
-                         const float* const* w1T, const float* const* w2T, const float* const* woT, float ln_eps, int B, int T,
-                         int D, const int* live, int layer, const void* step_state, int train, float p_drop, float* dpre2,
-                         float* dpre1, float* dr, float* d_o, float* ln_part, const void* sort_plan, int sort_phase, int mma_bf16, void* stream) {
-    AMID_CHECK_ARG(dxo && h && r && ln_w && w1T && w2T && woT && dpre2 && dpre1 && dr && d_o && ln_part && (!train || step_state));
+static int strip_ffn_bwd(const FfnBwdCall& c, const StripBwdLaunch& l) {
+    AMID_CHECK_ARG(c.dxo && c.operands());
+    const int D = l.D, mma_bf16 = l.mma_bf16;
     if (mma_bf16 && D != 128) return AMID_ERR_UNSUPPORTED;
     StripFfnBwdArgs a;
-    fill_ffn_bwd(a, dxo, tmq, h, r, ln_w, w1T, w2T, woT, ln_eps, layer, step_state, train, p_drop, dpre2, dpre1, dr, d_o, ln_part);
+    fill_ffn_bwd(a, c);
     StripGeom sg;
-    if (int e = make_strip_geom(B, T, D, live, &sg)) return e;
+    if (int e = make_strip_geom(l.B, l.T, D, l.live, &sg)) return e;
     SortRider rd;
-    if (int e = make_rider(rd, sort_plan, sort_phase)) return e;
+    if (int e = make_rider(rd, l.sort_plan, l.sort_phase)) return e;
     if (rd.phase != 0 && rd.phase != 2) return AMID_ERR_UNSUPPORTED;           // this launch carries phase 2
-    if (D == 128 && mma_bf16 == 3) return rd.phase ? launch_strip_rider<strip_ffn_bwd_kernel<128, 2, 3>, 128>(sg, rd, stream, a)
-                                                   : launch_strip_rider<strip_ffn_bwd_kernel<128, 0, 3>, 128>(sg, rd, stream, a);
-    if (D == 128 && mma_bf16) return rd.phase ? launch_strip_rider<strip_ffn_bwd_kernel<128, 2, 1>, 128>(sg, rd, stream, a)
-                                              : launch_strip_rider<strip_ffn_bwd_kernel<128, 0, 1>, 128>(sg, rd, stream, a);
-    if (D == 128 && rd.phase) return launch_strip_rider<strip_ffn_bwd_kernel<128, 2>, 128>(sg, rd, stream, a);
-    if (D == 128) return launch_strip_rider<strip_ffn_bwd_kernel<128, 0>, 128>(sg, rd, stream, a);
-    if (D == 64 && rd.phase) return launch_strip_rider<strip_ffn_bwd_kernel<64, 2>, 64>(sg, rd, stream, a);
-    if (D == 64) return launch_strip_rider<strip_ffn_bwd_kernel<64, 0>, 64>(sg, rd, stream, a);
+    if (D == 128) return mma_bf16 == 3 ? launch_ffn_bwd<128, 3>(sg, rd, l.stream, a) : mma_bf16 ? launch_ffn_bwd<128, 1>(sg, rd, l.stream, a)
+                                                                                          : launch_ffn_bwd<128, 0>(sg, rd, l.stream, a);
+    if (D == 64) return launch_ffn_bwd<64, 0>(sg, rd, l.stream, a);
     return AMID_ERR_UNSUPPORTED;
 }
 
@@ -732,8 +737,8 @@ extern "C" int amid_sas_strip_ffn_bwd_f32(const float* dxo, const unsigned char*
                                           const float* const* w1T, const float* const* w2T, const float* const* woT, float ln_eps, int B, int T,
                                           int D, const int* live, int layer, const void* step_state, int train, float p_drop, float* dpre2,
                                           float* dpre1, float* dr, float* d_o, float* ln_part, int mma_bf16, void* stream) {
-    return strip_ffn_bwd(dxo, tmq, h, r, ln_w, w1T, w2T, woT, ln_eps, B, T, D, live, layer, step_state, train, p_drop, dpre2, dpre1, dr, d_o,
-                         ln_part, nullptr, 0, mma_bf16, stream);
+    AMID_FFN_BWD_CALL(c); STRIP_BWD_LAUNCH(l);
+    return strip_ffn_bwd(c, l);
 }
 
 // ... carrying phase `sort_phase` (1 .. 4) of a sort plan (amid_sort_plan_pack) as extra workgroups in front of the tiles'
@@ -743,61 +748,71 @@ extern "C" int amid_sas_strip_ffn_bwd_sort_f32(const float* dxo, const unsigned 
                                                const void* step_state, int train, float p_drop, float* dpre2, float* dpre1, float* dr,
                                                float* d_o, float* ln_part, const void* sort_plan, int sort_phase, int mma_bf16, void* stream) {
     AMID_CHECK_ARG(sort_plan != nullptr);
-    return strip_ffn_bwd(dxo, tmq, h, r, ln_w, w1T, w2T, woT, ln_eps, B, T, D, live, layer, step_state, train, p_drop, dpre2, dpre1, dr, d_o,
-                         ln_part, sort_plan, sort_phase, mma_bf16, stream);
+    AMID_FFN_BWD_CALL(c); STRIP_BWD_LAUNCH(l); STRIP_BWD_RIDER(l);
+    return strip_ffn_bwd(c, l);
 }
 
-// fh != NULL: the layer below's feed-forward / out-projection backward (f* arguments) runs on d x in the same launch; dx is then not written
-static int strip_qkv_bwd(const float* dq, const float* dk, const float* dv, const float* dr, const float* x,
-                         const float* const* ln_w, const float* const* wqT, const float* const* wkT, const float* const* wvT,
-                         float ln_eps, int B, int T, int D, const int* live, float* dx, float* ln_part,
-                         const unsigned char* tmq, const float* fh, const float* fr, const float* const* fln_w,
-                         const float* const* fw1T, const float* const* fw2T, const float* const* fwoT, int flayer,
-                         const void* step_state, int train, float p_drop, float* fdpre2, float* fdpre1, float* fdr,
-                         float* fd_o, float* fln_part, const void* sort_plan, int sort_phase, int mma_bf16, void* stream,
-                         const unsigned char* emb_tmq = nullptr, float emb_p_drop = 0.f, const ScorerSum* scorer = nullptr) {
-    AMID_CHECK_ARG(dq && dk && dv && dr && x && ln_w && wqT && wkT && wvT && ln_part);
+// LayerNorm 1 / q / k / v backward of a layer as its entries state it; every field null / zero unless named.  Optional blocks:
+//   ffn (present: ffn.h != NULL): the layer below's feed-forward / out-projection backward runs on d x in the same launch; dx is then not
+//        written (its dxo, ln_eps, step_state and train are this record's: the entry names the rest);
+//   emb_tmq: the embedding layer's backward on the strip (StripQkvBwdArgs::emb_tmq), dropout rate emb_p_drop;
+//   scorer: the scorer's weight-gradient sums as further rider workgroups.
+struct StripQkvBwdCall {
+    const float* dq = nullptr; const float* dk = nullptr; const float* dv = nullptr; const float* dr = nullptr; const float* x = nullptr;
+    FamC ln_w = nullptr, wqT = nullptr, wkT = nullptr, wvT = nullptr;
+    float ln_eps = 0.f; float* dx = nullptr; float* ln_part = nullptr;
+    const void* step_state = nullptr; int train = 0;
+    FfnBwdCall ffn;
+    const unsigned char* emb_tmq = nullptr; float emb_p_drop = 0.f;
+    const ScorerSum* scorer = nullptr;
+};
+#define STRIP_QKV_BWD_CALL(c)                                                                                                                   \
+    StripQkvBwdCall c;                                                                                                                          \
+    c.dq = dq; c.dk = dk; c.dv = dv; c.dr = dr; c.x = x; c.ln_w = ln_w; c.wqT = wqT; c.wkT = wkT; c.wvT = wvT; c.ln_eps = ln_eps;                   \
+    c.ln_part = ln_part; c.step_state = step_state; c.train = train
+#define STRIP_QKV_BWD_FFN(c)                                                                                                                    \
+    c.ffn.tmq = tmq; c.ffn.h = fh; c.ffn.r = fr; c.ffn.ln_w = fln_w; c.ffn.w1T = fw1T; c.ffn.w2T = fw2T; c.ffn.woT = fwoT; c.ffn.layer = flayer;    \
+    c.ffn.p_drop = p_drop; c.ffn.dpre2 = fdpre2; c.ffn.dpre1 = fdpre1; c.ffn.dr = fdr; c.ffn.d_o = fd_o; c.ffn.ln_part = fln_part
+
+// (the rider's phase: 3 with the fused feed-forward backward, 4 without; the scorer sums' workgroups -- ss.nblk, 0 without them -- behind the sort's)
+template <int D, bool FFN, int BF>
+static int launch_qkv_bwd(const StripGeom& sg, const SortRider& rd, void* stream, const StripQkvBwdArgs& a, const StripFfnBwdArgs& f, const ScorerSum& ss) {
+    return rd.phase ? launch_strip_rider<strip_qkv_bwd_kernel<D, FFN, FFN ? 3 : 4, BF>, D>(sg, rd, ss.nblk, stream, a, f, ss)
+                    : launch_strip_rider<strip_qkv_bwd_kernel<D, FFN, 0, BF>, D>(sg, rd, 0, stream, a, f, ss);
+}
+static int strip_qkv_bwd(const StripQkvBwdCall& c, const StripBwdLaunch& l) {
+    AMID_CHECK_ARG(c.dq && c.dk && c.dv && c.dr && c.x && c.ln_w && c.wqT && c.wkT && c.wvT && c.ln_part);
+    const int D = l.D, mma_bf16 = l.mma_bf16;
     if (mma_bf16 && D != 128) return AMID_ERR_UNSUPPORTED;
-    const bool ffn = fh != nullptr;
-    AMID_CHECK_ARG(emb_tmq == nullptr || (!ffn && (!train || step_state)));
-    AMID_CHECK_ARG(ffn || dx);
-    AMID_CHECK_ARG(!ffn || (fr && fln_w && fw1T && fw2T && fwoT && fdpre2 && fdpre1 && fdr && fd_o && fln_part && (!train || step_state)));
+    const bool ffn = c.ffn.h != nullptr;
+    FfnBwdCall fc = c.ffn;
+    fc.dxo = nullptr; fc.ln_eps = c.ln_eps; fc.step_state = c.step_state; fc.train = c.train;
+    AMID_CHECK_ARG(c.emb_tmq == nullptr || (!ffn && (!c.train || c.step_state)));
+    AMID_CHECK_ARG(ffn || c.dx);
+    AMID_CHECK_ARG(!ffn || fc.operands());
     StripQkvBwdArgs a;
-    a.dq = dq; a.dk = dk; a.dv = dv; a.dr = dr; a.x = x; a.dx = dx; a.ln_part = ln_part; a.ln_eps = ln_eps;
-    for (int g = 0; g < 2; ++g) { a.ln_w[g] = ln_w[g]; a.wqT[g] = wqT[g]; a.wkT[g] = wkT[g]; a.wvT[g] = wvT[g]; }
-    a.emb_tmq = emb_tmq; a.emb_st = (const StepState*)step_state;
-    a.emb_train = (emb_tmq && train && emb_p_drop > 0.f) ? 1 : 0;
-    a.emb_spec = drop_spec(emb_p_drop);
-    a.emb_scale = a.emb_train ? 1.0f / (1.0f - emb_p_drop) : 1.0f;
+    a.dq = c.dq; a.dk = c.dk; a.dv = c.dv; a.dr = c.dr; a.x = c.x; a.dx = c.dx; a.ln_part = c.ln_part; a.ln_eps = c.ln_eps;
+    for (int g = 0; g < 2; ++g) { a.ln_w[g] = c.ln_w[g]; a.wqT[g] = c.wqT[g]; a.wkT[g] = c.wkT[g]; a.wvT[g] = c.wvT[g]; }
+    const DropoutArgs ed = dropout_args(c.emb_tmq && c.train, c.emb_p_drop);
+    a.emb_tmq = c.emb_tmq; a.emb_st = (const StepState*)c.step_state;
+    a.emb_train = ed.train; a.emb_spec = ed.spec; a.emb_scale = ed.scale;
     StripFfnBwdArgs f = {};
-    if (ffn) fill_ffn_bwd(f, nullptr, tmq, fh, fr, fln_w, fw1T, fw2T, fwoT, ln_eps, flayer, step_state, train, p_drop, fdpre2, fdpre1, fdr, fd_o, fln_part);
+    if (ffn) fill_ffn_bwd(f, fc);
     StripGeom sg;
-    if (int e = make_strip_geom(B, T, D, live, &sg)) return e;
+    if (int e = make_strip_geom(l.B, l.T, D, l.live, &sg)) return e;
     SortRider rd;
-    if (int e = make_rider(rd, sort_plan, sort_phase)) return e;
+    if (int e = make_rider(rd, l.sort_plan, l.sort_phase)) return e;
     if (rd.phase != 0 && rd.phase != (ffn ? 3 : 4)) return AMID_ERR_UNSUPPORTED;      // phase 3 with the fused feed-forward backward, 4 without
-    const bool ride = rd.phase != 0;
     ScorerSum ss = {};
-    if (scorer != nullptr) {
-        if (!(ride && ffn && D == 128 && (mma_bf16 == 3 || mma_bf16 == 1))) return AMID_ERR_UNSUPPORTED;       // the riders' host: the middle launch on bf16 pieces / one piece
-        ss = *scorer;
+    if (c.scorer != nullptr) {
+        if (!(rd.phase != 0 && ffn && D == 128 && (mma_bf16 == 3 || mma_bf16 == 1))) return AMID_ERR_UNSUPPORTED;       // the riders' host: the middle launch on bf16 pieces / one piece
+        ss = *c.scorer;
     }
-    if (D == 128 && mma_bf16 == 3 && ffn) return ride ? launch_strip_rider_x<strip_qkv_bwd_kernel<128, true, 3, 3>, 128>(sg, rd, ss.nblk, stream, a, f, ss)
-                                                      : launch_strip_rider<strip_qkv_bwd_kernel<128, true, 0, 3>, 128>(sg, rd, stream, a, f, ss);
-    if (D == 128 && mma_bf16 == 3) return ride ? launch_strip_rider<strip_qkv_bwd_kernel<128, false, 4, 3>, 128>(sg, rd, stream, a, f, ss)
-                                               : launch_strip_rider<strip_qkv_bwd_kernel<128, false, 0, 3>, 128>(sg, rd, stream, a, f, ss);
-    if (D == 128 && mma_bf16 && ffn) return ride ? launch_strip_rider_x<strip_qkv_bwd_kernel<128, true, 3, 1>, 128>(sg, rd, ss.nblk, stream, a, f, ss)
-                                                 : launch_strip_rider<strip_qkv_bwd_kernel<128, true, 0, 1>, 128>(sg, rd, stream, a, f, ss);
-    if (D == 128 && mma_bf16) return ride ? launch_strip_rider<strip_qkv_bwd_kernel<128, false, 4, 1>, 128>(sg, rd, stream, a, f, ss)
-                                          : launch_strip_rider<strip_qkv_bwd_kernel<128, false, 0, 1>, 128>(sg, rd, stream, a, f, ss);
-    if (D == 128 && ffn) return ride ? launch_strip_rider<strip_qkv_bwd_kernel<128, true, 3>, 128>(sg, rd, stream, a, f, ss)
-                                     : launch_strip_rider<strip_qkv_bwd_kernel<128, true, 0>, 128>(sg, rd, stream, a, f, ss);
-    if (D == 128) return ride ? launch_strip_rider<strip_qkv_bwd_kernel<128, false, 4>, 128>(sg, rd, stream, a, f, ss)
-                              : launch_strip_rider<strip_qkv_bwd_kernel<128, false, 0>, 128>(sg, rd, stream, a, f, ss);
-    if (D == 64 && ffn) return ride ? launch_strip_rider<strip_qkv_bwd_kernel<64, true, 3>, 64>(sg, rd, stream, a, f, ss)
-                                    : launch_strip_rider<strip_qkv_bwd_kernel<64, true, 0>, 64>(sg, rd, stream, a, f, ss);
-    if (D == 64) return ride ? launch_strip_rider<strip_qkv_bwd_kernel<64, false, 4>, 64>(sg, rd, stream, a, f, ss)
-                             : launch_strip_rider<strip_qkv_bwd_kernel<64, false, 0>, 64>(sg, rd, stream, a, f, ss);
+    void* const st = l.stream;
+    if (D == 128 && mma_bf16 == 3) return ffn ? launch_qkv_bwd<128, true, 3>(sg, rd, st, a, f, ss) : launch_qkv_bwd<128, false, 3>(sg, rd, st, a, f, ss);
+    if (D == 128 && mma_bf16) return ffn ? launch_qkv_bwd<128, true, 1>(sg, rd, st, a, f, ss) : launch_qkv_bwd<128, false, 1>(sg, rd, st, a, f, ss);
+    if (D == 128) return ffn ? launch_qkv_bwd<128, true, 0>(sg, rd, st, a, f, ss) : launch_qkv_bwd<128, false, 0>(sg, rd, st, a, f, ss);
+    if (D == 64) return ffn ? launch_qkv_bwd<64, true, 0>(sg, rd, st, a, f, ss) : launch_qkv_bwd<64, false, 0>(sg, rd, st, a, f, ss);
     return AMID_ERR_UNSUPPORTED;
 }
 
@@ -808,8 +823,8 @@ extern "C" int amid_sas_strip_qkv_bwd_f32(const float* dq, const float* dk, cons
                                           const float* const* fw1T, const float* const* fw2T, const float* const* fwoT, int flayer,
                                           const void* step_state, int train, float p_drop, float* fdpre2, float* fdpre1, float* fdr,
                                           float* fd_o, float* fln_part, int mma_bf16, void* stream) {
-    return strip_qkv_bwd(dq, dk, dv, dr, x, ln_w, wqT, wkT, wvT, ln_eps, B, T, D, live, dx, ln_part, tmq, fh, fr, fln_w, fw1T, fw2T, fwoT, flayer,
-                         step_state, train, p_drop, fdpre2, fdpre1, fdr, fd_o, fln_part, nullptr, 0, mma_bf16, stream);
+    STRIP_QKV_BWD_CALL(c); STRIP_QKV_BWD_FFN(c); c.dx = dx; STRIP_BWD_LAUNCH(l);
+    return strip_qkv_bwd(c, l);
 }
 
 // ... carrying phase `sort_phase` (1 .. 4) of a sort plan (amid_sort_plan_pack) as extra workgroups in front of the tiles'
@@ -822,8 +837,8 @@ extern "C" int amid_sas_strip_qkv_bwd_sort_f32(const float* dq, const float* dk,
                                                float* fdpre2, float* fdpre1, float* fdr, float* fd_o, float* fln_part, const void* sort_plan,
                                                int sort_phase, int mma_bf16, void* stream) {
     AMID_CHECK_ARG(sort_plan != nullptr);
-    return strip_qkv_bwd(dq, dk, dv, dr, x, ln_w, wqT, wkT, wvT, ln_eps, B, T, D, live, dx, ln_part, tmq, fh, fr, fln_w, fw1T, fw2T, fwoT, flayer,
-                         step_state, train, p_drop, fdpre2, fdpre1, fdr, fd_o, fln_part, sort_plan, sort_phase, mma_bf16, stream);
+    STRIP_QKV_BWD_CALL(c); STRIP_QKV_BWD_FFN(c); c.dx = dx; STRIP_BWD_LAUNCH(l); STRIP_BWD_RIDER(l);
+    return strip_qkv_bwd(c, l);
 }
 
 // amid_sas_strip_qkv_bwd_sort_f32 (with the fused feed-forward backward: phase 3 of the sort plan) carrying, as further extra workgroups,
@@ -843,8 +858,8 @@ extern "C" int amid_sas_strip_qkv_bwd_sort_scorer_f32(const float* dq, const flo
     AMID_CHECK_ARG(sort_plan != nullptr && fh != nullptr && hidg && u && items && NI > 0 && hid > 0 && dW1 && db1 && dW2 && db2);
     AMID_CHECK_ARG(((((unsigned long long)dW1) | ((unsigned long long)u) | ((unsigned long long)items)) & 15) == 0);
     const ScorerSum ss = scorer_sum_args(hidg, u, items, B, NI, D, hid, dW1, db1, dW2, db2);
-    return strip_qkv_bwd(dq, dk, dv, dr, x, ln_w, wqT, wkT, wvT, ln_eps, B, T, D, live, nullptr, ln_part, tmq, fh, fr, fln_w, fw1T, fw2T, fwoT, flayer,
-                         step_state, train, p_drop, fdpre2, fdpre1, fdr, fd_o, fln_part, sort_plan, sort_phase, mma_bf16, stream, nullptr, 0.f, &ss);
+    STRIP_QKV_BWD_CALL(c); STRIP_QKV_BWD_FFN(c); c.scorer = &ss; STRIP_BWD_LAUNCH(l); STRIP_BWD_RIDER(l);
+    return strip_qkv_bwd(c, l);
 }
 
 // layer 0's launch of the live-sequence train step with the embedding layer's backward on the strip (StripQkvBwdArgs::emb_tmq): dx = the
@@ -857,10 +872,14 @@ extern "C" int amid_sas_strip_qkv_bwd_emb_f32(const float* dq, const float* dk, 
                                               float* ln_part, const unsigned char* emb_tmq, const void* step_state, int train,
                                               float emb_p_drop, const void* sort_plan, int sort_phase, int mma_bf16, void* stream) {
     AMID_CHECK_ARG(emb_tmq != nullptr && dx != nullptr);
-    return strip_qkv_bwd(dq, dk, dv, dr, x, ln_w, wqT, wkT, wvT, ln_eps, B, T, D, live, dx, ln_part, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, 0, step_state, train, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, sort_plan, sort_phase, mma_bf16,
-                         stream, emb_tmq, emb_p_drop);
+    STRIP_QKV_BWD_CALL(c); c.dx = dx; c.emb_tmq = emb_tmq; c.emb_p_drop = emb_p_drop; STRIP_BWD_LAUNCH(l); STRIP_BWD_RIDER(l);
+    return strip_qkv_bwd(c, l);
 }
+#undef AMID_FFN_BWD_CALL
+#undef STRIP_QKV_BWD_FFN
+#undef STRIP_QKV_BWD_CALL
+#undef STRIP_BWD_RIDER
+#undef STRIP_BWD_LAUNCH
 
 // ---- the fused per-sequence backward ------------------------------------------------------------------------------------------------
 template <int D> static constexpr size_t seq_bwd_lds_bytes() { return strip_lds_bytes<D>() + (size_t)STRIP_WAVES * ATTN_BWD_LDS_PER_WAVE; }
@@ -915,8 +934,11 @@ extern "C" int amid_sas_seq_bwd_f32(int n_layers, const float* dxo, const unsign
             const int i = 2 * l + g;
             AMID_CHECK_ARG(ln1_w[i] && ln2_w[i] && wqT[i] && wkT[i] && wvT[i] && woT[i] && w1T[i] && w2T[i]);
         }
-        fill_ffn_bwd(P.f, l + 1 == n_layers ? dxo : nullptr, tmq, h[l], r[l], ln2_w + 2 * l, w1T + 2 * l, w2T + 2 * l, woT + 2 * l, ln_eps, l,
-                     step_state, train, p_drop, dpre2[l], dpre1[l], dr[l], d_o, ln2_part[l]);
+        FfnBwdCall fc;
+        fc.dxo = l + 1 == n_layers ? dxo : nullptr; fc.tmq = tmq; fc.h = h[l]; fc.r = r[l]; fc.ln_w = ln2_w + 2 * l; fc.w1T = w1T + 2 * l;
+        fc.w2T = w2T + 2 * l; fc.woT = woT + 2 * l; fc.ln_eps = ln_eps; fc.layer = l; fc.step_state = step_state; fc.train = train; fc.p_drop = p_drop;
+        fc.dpre2 = dpre2[l]; fc.dpre1 = dpre1[l]; fc.dr = dr[l]; fc.d_o = d_o; fc.ln_part = ln2_part[l];
+        fill_ffn_bwd(P.f, fc);
         P.a.dq = dq[l]; P.a.dk = dk[l]; P.a.dv = dv[l]; P.a.dr = dr[l]; P.a.x = x[l]; P.a.dx = l == 0 ? dx : nullptr;
         P.a.ln_part = ln1_part[l]; P.a.ln_eps = ln_eps;
         for (int g = 0; g < 2; ++g) {
@@ -928,9 +950,8 @@ extern "C" int amid_sas_seq_bwd_f32(int n_layers, const float* dxo, const unsign
         at.B = B; at.T = T; at.D = D; at.H = H; at.causal = 1; at.layer = l;
         at.scale = sqrtf(1.0f / (float)(D / H));
         at.st = (const StepState*)step_state;
-        at.train = (train && p_drop > 0.f) ? 1 : 0;
-        at.thr16 = drop_spec(p_drop);
-        at.dscale = at.train ? 1.0f / (1.0f - p_drop) : 1.0f;
+        const DropoutArgs ad = dropout_args(train, p_drop);
+        at.train = ad.train; at.thr16 = ad.spec; at.dscale = ad.scale;
         at.stagger_from = -1;
     }
     StripGeom sg;
@@ -939,11 +960,6 @@ extern "C" int amid_sas_seq_bwd_f32(int n_layers, const float* dxo, const unsign
         const int rc = launch_seqn_bwd(a, sg, D, mma_bf16, stream);      // section 5.0; T <= 32 and D 64: the N-split build only)
         if (rc != AMID_ERR_UNSUPPORTED || T <= 32 || D != 128) return rc;
     }
-    static unsigned long long attr_done[2] = {0, 0};
-    if (int rc = mma_bf16 ? lds_attr_once((const void*)seq_bwd_kernel<128, true>, seq_bwd_lds_bytes<128>(), attr_done[1])
-                          : lds_attr_once((const void*)seq_bwd_kernel<128, false>, seq_bwd_lds_bytes<128>(), attr_done[0])) return rc;
-    if (mma_bf16) seq_bwd_kernel<128, true><<<B, STRIP_THREADS, seq_bwd_lds_bytes<128>(), (hipStream_t)stream>>>(a, sg);
-    else seq_bwd_kernel<128, false><<<B, STRIP_THREADS, seq_bwd_lds_bytes<128>(), (hipStream_t)stream>>>(a, sg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AMID_OK : (int)e;
+    return mma_bf16 ? launch_lds<seq_bwd_kernel<128, true>>(B, STRIP_THREADS, seq_bwd_lds_bytes<128>(), stream, a, sg)
+                    : launch_lds<seq_bwd_kernel<128, false>>(B, STRIP_THREADS, seq_bwd_lds_bytes<128>(), stream, a, sg);
 }

@@ -227,18 +227,6 @@ __global__ __launch_bounds__(PXB_THREADS) void strip_ffn_bwd_px_kernel(const Str
 using namespace amid;
 using namespace amid_strip_host;
 
-static void pxb_fill_ffn_bwd(StripFfnBwdArgs& a, const float* dxo, const unsigned char* tmq, const float* h, const float* r,
-                             const float* const* ln_w, const float* const* w1T, const float* const* w2T, const float* const* woT, float ln_eps,
-                             int layer, const void* step_state, int train, float p_drop, float* dpre2, float* dpre1, float* dr, float* d_o,
-                             float* ln_part) {
-    a.dxo = dxo; a.tmq = tmq; a.h = h; a.r = r; a.dpre2 = dpre2; a.dpre1 = dpre1; a.dr = dr; a.d_o = d_o; a.ln_part = ln_part;
-    a.ln_eps = ln_eps; a.st = (const StepState*)step_state; a.layer = layer;
-    a.train = (train && p_drop > 0.f) ? 1 : 0;
-    a.spec = drop_spec(p_drop);
-    a.scale = a.train ? 1.0f / (1.0f - p_drop) : 1.0f;
-    for (int g = 0; g < 2; ++g) { a.ln_w[g] = ln_w[g]; a.w1T[g] = w1T[g]; a.w2T[g] = w2T[g]; a.woT[g] = woT[g]; }
-}
-
 // amid_sas_strip_ffn_bwd_f32 (mma_bf16 = 3: the weights are three-plane images of the transposes) as the N-split build on pieces.
 // ln_stat: the forward's row statistics of this layer ([2 B T][4]: LN2's mean and rstd at +2) or NULL.  sort_plan / sort_phase: optional rider.
 extern "C" int amid_sas_strip_ffn_bwd_px_f32(const float* dxo, const unsigned char* tmq, const float* h, const float* r, const float* const* ln_w,
@@ -246,13 +234,14 @@ extern "C" int amid_sas_strip_ffn_bwd_px_f32(const float* dxo, const unsigned ch
                                              int D, const int* live, int layer, const void* step_state, int train, float p_drop, float* dpre2,
                                              float* dpre1, float* dr, float* d_o, float* ln_part, const float* ln_stat, const void* sort_plan,
                                              int sort_phase, void* stream) {
-    AMID_CHECK_ARG(dxo && h && r && ln_w && w1T && w2T && woT && dpre2 && dpre1 && dr && d_o && ln_part && (!train || step_state));
+    AMID_FFN_BWD_CALL(c);
+    AMID_CHECK_ARG(c.dxo && c.operands());
     if (D != 128) return AMID_ERR_UNSUPPORTED;
     if (train && p_drop > 0.f && spec_bits(drop_spec(p_drop)) != 1) return AMID_ERR_UNSUPPORTED;       // part_dropout: p = 0.5
     StripGeom sg;
     if (int e = make_strip_geom(B, T, D, live, &sg)) return e;
     StripFfnBwdArgs a;
-    pxb_fill_ffn_bwd(a, dxo, tmq, h, r, ln_w, w1T, w2T, woT, ln_eps, layer, step_state, train, p_drop, dpre2, dpre1, dr, d_o, ln_part);
+    fill_ffn_bwd(a, c);
     SortRider rd;
     rd.phase = 0;
     if (sort_plan != nullptr) {
@@ -262,15 +251,7 @@ extern "C" int amid_sas_strip_ffn_bwd_px_f32(const float* dxo, const unsigned ch
     }
     constexpr size_t lds = pxb_lds_floats<128>() * sizeof(float);
     static_assert(lds >= sizeof(SortScatterLds<OS_BINS_MAX>), "the rider's scatter fits the head of the allocation");
-    if (rd.phase != 0) {
-        static unsigned long long done = 0;
-        if (int rc = lds_attr_once((const void*)strip_ffn_bwd_px_kernel<128, 2>, lds, done)) return rc;
-        strip_ffn_bwd_px_kernel<128, 2><<<2 * sg.tpg + rd.plan.nblk, PXB_THREADS, lds, (hipStream_t)stream>>>(a, ln_stat, sg, rd);
-    } else {
-        static unsigned long long done = 0;
-        if (int rc = lds_attr_once((const void*)strip_ffn_bwd_px_kernel<128, 0>, lds, done)) return rc;
-        strip_ffn_bwd_px_kernel<128, 0><<<2 * sg.tpg, PXB_THREADS, lds, (hipStream_t)stream>>>(a, ln_stat, sg, rd);
-    }
-    AMID_LAUNCH_CHECK();
-    return AMID_OK;
+    if (rd.phase != 0) return launch_lds<strip_ffn_bwd_px_kernel<128, 2>>(2 * sg.tpg + rd.plan.nblk, PXB_THREADS, lds, stream, a, ln_stat, sg, rd);
+    return launch_lds<strip_ffn_bwd_px_kernel<128, 0>>(2 * sg.tpg, PXB_THREADS, lds, stream, a, ln_stat, sg, rd);
 }
+#undef AMID_FFN_BWD_CALL

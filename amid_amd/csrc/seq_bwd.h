@@ -4,6 +4,7 @@
 #include "common.h"
 #include "strip_gemm.h"
 #include "attention_mfma.h"
+#include "host_launch.h"
 
 namespace amid {
 
@@ -38,6 +39,31 @@ struct SeqBwdLayer {
     AttnArgs at;
 };
 struct SeqBwdArgs { SeqBwdLayer L[2]; int n_layers; };
+
+// ---- host side: the feed-forward / out-projection backward of a layer as an entry point states it (the operands of
+// amid_sas_strip_ffn_bwd_f32); every field null / zero unless named.  Inside StripQkvBwdCall it is the optional fused block (absent: h == NULL).
+struct FfnBwdCall {
+    const float* dxo = nullptr; const unsigned char* tmq = nullptr; const float* h = nullptr; const float* r = nullptr;
+    FamC ln_w = nullptr, w1T = nullptr, w2T = nullptr, woT = nullptr;
+    float ln_eps = 0.f; int layer = 0;
+    const void* step_state = nullptr; int train = 0; float p_drop = 0.f;
+    float* dpre2 = nullptr; float* dpre1 = nullptr; float* dr = nullptr; float* d_o = nullptr; float* ln_part = nullptr;
+    // everything but dxo (a fused block takes its gradient from the chain in front of it)
+    bool operands() const { return h && r && ln_w && w1T && w2T && woT && dpre2 && dpre1 && dr && d_o && ln_part && (!train || step_state); }
+};
+// a record `f` bound to an entry point's parameters of the same names
+#define AMID_FFN_BWD_CALL(f)                                                                                                                   \
+    FfnBwdCall f;                                                                                                                              \
+    f.dxo = dxo; f.tmq = tmq; f.h = h; f.r = r; f.ln_w = ln_w; f.w1T = w1T; f.w2T = w2T; f.woT = woT; f.ln_eps = ln_eps; f.layer = layer;           \
+    f.step_state = step_state; f.train = train; f.p_drop = p_drop; f.dpre2 = dpre2; f.dpre1 = dpre1; f.dr = dr; f.d_o = d_o; f.ln_part = ln_part
+
+static inline void fill_ffn_bwd(StripFfnBwdArgs& a, const FfnBwdCall& c) {
+    a.dxo = c.dxo; a.tmq = c.tmq; a.h = c.h; a.r = c.r; a.dpre2 = c.dpre2; a.dpre1 = c.dpre1; a.dr = c.dr; a.d_o = c.d_o; a.ln_part = c.ln_part;
+    a.ln_eps = c.ln_eps; a.st = (const StepState*)c.step_state; a.layer = c.layer;
+    const DropoutArgs d = dropout_args(c.train, c.p_drop);
+    a.train = d.train; a.spec = d.spec; a.scale = d.scale;
+    for (int g = 0; g < 2; ++g) { a.ln_w[g] = c.ln_w[g]; a.w1T[g] = c.w1T[g]; a.w2T[g] = c.w2T[g]; a.woT[g] = c.woT[g]; }
+}
 
 // the N-split build of the one-launch backward (sasrec_seqn_bwd.hip); AMID_ERR_UNSUPPORTED when it does not cover the arguments
 int launch_seqn_bwd(const SeqBwdArgs& a, const StripGeom& sg, int D, int mma_bf16, void* stream);

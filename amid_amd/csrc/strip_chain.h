@@ -5,6 +5,7 @@
 #include "common.h"
 #include "rng.h"
 #include "strip_gemm.h"
+#include "host_launch.h"
 #include <type_traits>
 
 namespace amid {
@@ -163,13 +164,11 @@ static int make_strip_geom(int B, int T, int D, const int* live, StripGeom* sg) 
     return AMID_OK;
 }
 
+// a strip launch: a workgroup per tile of the two domains, the geometry as the kernel's last argument (launches with further workgroups --
+// riders, prologues -- state their grid to launch_lds themselves)
 template <auto KERNEL, int DVAL, class... Args>
 static int launch_strip(const StripGeom& sg, void* stream, const Args&... args) {
-    static unsigned long long attr_done = 0;
-    if (int rc = lds_attr_once((const void*)KERNEL, strip_lds_bytes<DVAL>(), attr_done)) return rc;
-    KERNEL<<<2 * sg.tpg, STRIP_THREADS, strip_lds_bytes<DVAL>(), (hipStream_t)stream>>>(args..., sg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AMID_OK : (int)e;
+    return launch_lds<KERNEL>(2 * sg.tpg, STRIP_THREADS, strip_lds_bytes<DVAL>(), stream, args..., sg);
 }
 
 }  // namespace amid_strip_host

@@ -565,3 +565,42 @@ def test_comp_module_surface():
         assert relmax(p1, w1) < 1e-4 and relmax(p2, w2) < 1e-4
     with pytest.raises(ValueError):      # trans_bs is Linear(bs, 1) over the batch: other batch sizes cannot run (as in the reference)
         m(None, b["i_node"][:4].cuda(), b["neg_samples"][:4].cuda(), b["seq_d1"][:4].cuda(), b["seq_d2"][:4].cuda(), None, None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", [12, 20, 40])      # one, two and three strips of a 64-row tile's sequences; B T = 36, 60, 120: no multiple of the tile
+def test_projection_strip_without_a_prologue_equals_the_prologue_entry_given_none(T):
+    """amid_bert_strip_qkv_fwd_f32 is amid_bert_strip_qkv_fwd_pro_f32 with no key-keep bytes and no transposes riding: the same call record
+    but for the (absent) prologue block, so y, q, k, v come out BIT FOR BIT -- over a live list with both domains on it (the dead rows stay
+    untouched) and over every row."""
+    from amid_amd._lib import lib, ptr_array
+    L, B, D = lib(), 3, 128
+    M, s = B * T, torch.cuda.current_stream().cuda_stream
+    g = torch.Generator().manual_seed(900 + T)
+    x = torch.randn(2 * M, D, generator=g).cuda()
+    vec = lambda base: [(base + 0.1 * torch.randn(D, generator=g)).cuda() for _ in range(2)]      # noqa: E731
+    la, lb = vec(1.0), vec(0.0)
+    w3 = [(0.1 * torch.randn(D, D, generator=g)).cuda() for _ in range(6)]                         # [q, k, v][domain]
+    b3 = [(0.1 * torch.randn(D, generator=g)).cuda() for _ in range(6)]
+    P = lambda ts: ptr_array([t.data_ptr() for t in ts])      # noqa: E731
+    live = torch.tensor([0, 2, 1, 2], dtype=torch.int32).cuda()      # domain 0: sequences 0 and 2, domain 1: sequence 1; n0 = 2
+    for lv in (live.data_ptr(), None):
+        got = {}
+        for entry in ("amid_bert_strip_qkv_fwd_f32", "amid_bert_strip_qkv_fwd_pro_f32"):
+            out = [torch.full((2 * M, D), float("nan"), device="cuda") for _ in range(4)]       # y, q, k, v
+            tail = (None, 0, None, None, None, None, None, 0) if "pro" in entry else ()
+            L.call(entry, x.data_ptr(), P(la), P(lb), P(w3), P(b3), B, T, lv, *[t.data_ptr() for t in out], *tail, s)
+            torch.cuda.synchronize()
+            got[entry] = [t.cpu() for t in out]
+        for name, a, b in zip("yqkv", *got.values()):
+            assert torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b)), (name, lv is not None)
+            assert torch.isfinite(a).any(), name
+        # ... and the result is right: the row-tile kernel (amid_bert_qkv_fwd_f32, held to the oracle elsewhere in this file) on the same
+        # inputs, to rounding (the two sum over k in different orders: the strip tests' bar)
+        ref = [torch.full((2 * M, D), float("nan"), device="cuda") for _ in range(4)]
+        L.call("amid_bert_qkv_fwd_f32", x.data_ptr(), P(la), P(lb), P(w3), P(b3), M, L.value("amid_rows_per_tile", M), *[t.data_ptr() for t in ref], s)
+        torch.cuda.synchronize()
+        rows = torch.ones(2 * M, dtype=torch.bool) if lv is None else torch.tensor([1, 0, 1, 0, 1, 0], dtype=torch.bool).repeat_interleave(T)
+        for name, a, b in zip("yqkv", got["amid_bert_strip_qkv_fwd_f32"], ref):
+            assert torch.isfinite(a[rows]).all() and torch.isnan(a[~rows]).all(), (name, lv is not None)
+            assert relmax(a[rows], b.cpu()[rows]) < 3e-6, (name, relmax(a[rows], b.cpu()[rows]))

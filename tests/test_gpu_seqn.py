@@ -217,3 +217,61 @@ def test_bf16_products_stay_within_bf16_rounding_of_the_fp32_forward(B, T, varia
             if bool((~rl).any()):
                 assert torch.isnan(got[name][~rl]).all(), f"variant {v} {name}: rows outside the live list were written"
         assert worst > 1e-4, "bf16 products left no trace: the fp32 kernel ran"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", [20, 40])      # the two builds that multiply single pieces (two and four strips a sequence; none at T <= 16)
+def test_one_piece_gather_forward_equals_its_sibling_with_the_head_on_the_tail(T):
+    """amid_sas_seq_fwd_gather_p1_f32 and amid_sas_seq_fwd_gather_head_p1_f32 state the same call record but for the (absent) head block:
+    the same one-piece products over the same gathered rows.  Two engines take the same folded bf16 step, one with the head on the
+    forward's workgroups (keeping the output rows), one without; at the forward launch each engine's own call is made with dropout on
+    (p = 0.5) and again with train = 0, and what it left is read before the step goes on: the gathered rows, the mask bytes, the output
+    rows, q, k, v, o, the softmax and row statistics, r and h agree BIT FOR BIT.  The plan's buffers are torch.empty and a forward over
+    the live list writes only the rows of a sequence in its own domain, so they are filled with NaN / 0xFF first and the rows of the
+    other domain must come back untouched.  Both domains are live; one sequence's other-domain half is all padding."""
+    from amid_amd._lib import lib, parse_header
+    from oracle import amid_oracle as orc
+    from tests.test_gpu_timed_path import make_engine, split_batch, timed_pool_step
+    B, D, hid, n_items = 3, 128, 32, 3000
+    P = orc.random_params(orc.sasrec_param_shapes(n_items, D, T, hid), seed=70 + T)
+    batch = split_batch(B, T, n_items, seed=7 + T, split="mixed")
+    batch["domain_id"] = torch.tensor([0, 1, 0])
+    batch["seq_d2"][0, :] = n_items - 1
+    row_live = torch.cat((batch["domain_id"] == 0, batch["domain_id"] != 0)).repeat_interleave(T)
+    got = {}
+    for head in (True, False):
+        eng = make_engine(P, T, seed=5, compute="bf16")
+        eng.HEAD_ON_FWD, eng.HEAD_ON_FWD_KEEPS_X = head, True
+        pl = eng.plan(B, T, 2, need_grad=True)
+        L = lib()
+        fwd = "amid_sas_seq_fwd_gather_head_p1_f32" if head else "amid_sas_seq_fwd_gather_p1_f32"
+        i_train = parse_header()[fwd][2].index("train")
+        saved = lambda: [pl.x[0], pl.tmq, pl.x[2], *pl.q, *pl.k, *pl.v, *pl.o, *pl.stats, *pl.r, *pl.h, *pl.ln_stat]      # noqa: E731
+        snap, orig = [], L.call
+
+        def spy(name, *a):
+            if name != fwd:
+                return orig(name, *a)
+            for train in (0, a[i_train]):                       # (the step's own call last: the step goes on from what it left)
+                torch.cuda.synchronize()
+                for t in saved():
+                    t.fill_(float("nan") if t.is_floating_point() else 255)
+                torch.cuda.synchronize()
+                rc = orig(name, *a[:i_train], train, *a[i_train + 1:])
+                torch.cuda.synchronize()
+                snap.append([t.clone().cpu() for t in saved()])
+            return rc
+        L.call = spy
+        try:
+            timed_pool_step(eng, pl, batch, 3, 5)
+        finally:
+            del L.call
+        assert len(snap) == 2, fwd
+        got[head] = snap[0] + snap[1]
+    n = len(got[True]) // 2
+    for i, (a, b) in enumerate(zip(got[True], got[False])):
+        rows = a.reshape(2 * B * T, -1)
+        if a.is_floating_point():
+            assert torch.isfinite(rows[row_live]).all() and torch.isnan(rows[~row_live]).all(), i
+        assert torch.equal(torch.nan_to_num(a.float()), torch.nan_to_num(b.float())), i
+    assert not torch.equal(torch.nan_to_num(got[False][2]), torch.nan_to_num(got[False][n + 2]))      # (dropout did something)

@@ -352,3 +352,35 @@ def test_strip_backward_n_split_build_on_pieces_matches_the_strip_build(B, T, li
         t_px = timeit(lambda: L.call("amid_sas_strip_ffn_bwd_px_f32", dxo.data_ptr(), c.tmq.data_ptr(), h.data_ptr(), r.data_ptr(), P(lnw), I(0), I(1), I(2), 1e-8,
                                      B, T, D, c.lp(), 1, c.st.data_ptr(), 1, 0.5, *[t.data_ptr() for t in out], pg.data_ptr(), stat.data_ptr(), None, 0, s))
         print(f"PXTIME strip_ffn_bwd: strip build {t_strip:.1f} us, n-split on pieces {t_px:.1f} us (launch-to-launch, eager)")
+
+
+@pytest.mark.parametrize("T", [12, 20, 40])          # one, two and three waves of a strip tile's sequences; B T = 36, 60, 120: no multiple of the tile
+@pytest.mark.parametrize("D", [128, 64])
+@pytest.mark.parametrize("train", [1, 0])            # embedding dropout 0.5 / off
+def test_embedding_backward_on_the_strip_without_a_rider_equals_its_two_launches(T, D, train):
+    """amid_sas_strip_qkv_bwd_emb_f32 with sort_plan == NULL (the form no step of the engine takes: its launches always carry the sort) is
+    amid_sas_strip_qkv_bwd_f32 without the fused feed-forward followed by amid_embed_bwd_f32's element-wise part on the stored rows: the
+    same call record with the embedding block named and no rider.  dx of the live sequences and the LayerNorm partial sums BIT FOR BIT;
+    the rows outside the live list stay untouched.  Both domains are on the list."""
+    B = 3
+    c = Ctx(B, T, D, seed=40 + T + D, live="mixed")
+    c.dom = torch.tensor([0, 1, 0])
+    c.live = torch.tensor([0, 2, 1, 2], dtype=torch.int32).cuda()      # domain 0: sequences 0 and 2; domain 1: sequence 1; n0 = 2
+    c.row_live = torch.cat((c.dom == 0, c.dom != 0)).repeat_interleave(T)
+    L, pa, s = c.L, c.pa, c.s
+    P = lambda t: pa([t[0].data_ptr(), t[1].data_ptr()])      # noqa: E731
+    dq, dk, dv, dr = (c.act(live_only=True) for _ in range(4))
+    x, lnw, wq, wk, wv = c.act(), c.vec(1.0), c.mat(), c.mat(), c.mat()
+    part = lambda: torch.full((2 * c.stpg, 2, D), float("nan"), device="cuda")      # noqa: E731
+    two, one, p2, p1 = c.out(), c.out(), part(), part()
+    head = (dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dr.data_ptr(), x.data_ptr(), P(lnw), P(wq), P(wk), P(wv), 1e-8, B, T, D, c.lp())
+    L.call("amid_sas_strip_qkv_bwd_f32", *head, two.data_ptr(), p2.data_ptr(), *([None] * 7), 0, None, 0, 0.0, *([None] * 5), 0, s)
+    dpos = torch.zeros(1, 2, T, D, device="cuda")
+    L.call("amid_embed_bwd_f32", two.data_ptr(), c.tmq.data_ptr(), B, T, D, 1, dpos.data_ptr(), c.st.data_ptr(), train, 0.5, s)
+    L.call("amid_sas_strip_qkv_bwd_emb_f32", *head, one.data_ptr(), p1.data_ptr(), c.tmq.data_ptr(), c.st.data_ptr(), train, 0.5, None, 0, 0, s)
+    torch.cuda.synchronize()
+    rl = c.row_live
+    assert torch.isfinite(one.cpu()[rl]).all() and bool((one.cpu()[rl] == 0).any()) and bool((one.cpu()[rl] != 0).any())
+    assert torch.equal(one.cpu()[rl], two.cpu()[rl])
+    assert torch.isnan(one.cpu()[~rl]).all(), "rows outside the live list were written"
+    assert torch.equal(torch.nan_to_num(p1.cpu()), torch.nan_to_num(p2.cpu())) and torch.equal(torch.isnan(p1.cpu()), torch.isnan(p2.cpu()))
