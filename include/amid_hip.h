@@ -392,7 +392,10 @@ int amid_sample_negatives_i64(const long long* pool_d1, int n_pool_d1, const lon
  *   mix_fwd : gate = softmax_batch(s) > threshold (:490-491); z_g = sum_j w_bs_g[j] gate_j u_raw[1-g][j];
  *             u_mix[g][b] = 0.5 u_raw[g][b] + 0.5 (W_nn_g z_g + b_nn_g sum_j w_bs_g[j] + b_bs_g)        (:492-495, :432-434)
  *   mix_bwd : gradients of the above into du_raw and the eight InterComp parameters (written whole, no partials).
- * Host pointer arrays hold 2 device pointers: index 0 = itc_d1 / sac1, 1 = itc_d2 / sac2.  u_raw: amid_lnmean_fwd_f32. */
+ * Host pointer arrays hold 2 device pointers: index 0 = itc_d1 / sac1, 1 = itc_d2 / sac2.  u_raw: amid_lnmean_fwd_f32.
+ * All three: D % 4 == 0 and D <= 128 (a row is 32 lanes of one float4), AMID_ERR_UNSUPPORTED above -- the pair-max also when
+ * 2 T (D + 4) floats exceed 160 KiB - 256 bytes of LDS (T <= 154 at D = 128), the mix forward when a batch outside its
+ * 512-thread form (32 <= B <= 256, D 64 / 128) needs more than 60 KiB (B > 6656 at D = 128). */
 int amid_itc_pairmax_f32(const float* x, const float* const* ln_w, const float* const* ln_b, int B, int T, int D, float eps, float* s,
                          float* u_raw /* optional [2, B, D]: also emit mean_t LN_last(x), saving the amid_lnmean_fwd_f32 launch */,
                          void* stream);

@@ -92,3 +92,21 @@ def test_round6_entry_points_refuse_bad_arguments_without_a_gpu():
     # the inference forward: no piece images ; the evaluation head: no table
     assert L._fn["amid_sas_seq_fwd_split_infer_f32"](2, null, null, *[null] * 12, null, 1e-8, 4, 40, 128, 8, null, null, null) == -1
     assert L._fn["amid_eval_head_f32"](*[null] * 11, 4, 40, 100, 128, 32, 1e-8, 1e-7, null, null, null, null, null, null) == -1
+
+
+def test_intercomp_entry_points_refuse_wide_rows_without_a_gpu():
+    """InterComp's three entry points give a row 32 lanes of one float4: D > 128 is AMID_ERR_UNSUPPORTED from each of them (the mix entries
+    used to run it over the first 128 columns and return AMID_OK), as is a pair-max whose rows do not fit in LDS -- all before anything touches
+    a device, so the pointers are never followed."""
+    import ctypes
+    L = _lib.lib()
+    p = ctypes.c_void_p(0x1000)
+    pair = (ctypes.c_void_p * 2)(0x1000, 0x1000)
+    for D in (132, 256, 1024):
+        assert L._fn["amid_itc_pairmax_f32"](p, pair, pair, 8, 20, D, 1e-8, p, p, None) == -2, D
+        for B in (8, 48, 256, 300):
+            assert L._fn["amid_itc_mix_fwd_f32"](p, p, pair, pair, pair, pair, 0.5, B, D, p, p, p, p, None) == -2, (B, D)
+            assert L._fn["amid_itc_mix_bwd_f32"](p, p, p, p, p, pair, pair, pair, B, D, p, pair, pair, pair, pair, None) == -2, (B, D)
+    assert L._fn["amid_itc_pairmax_f32"](p, pair, pair, 8, 155, 128, 1e-8, p, p, None) == -2          # 2 * 155 * 132 floats: over 160 KiB - 256
+    assert L._fn["amid_itc_mix_fwd_f32"](p, p, pair, pair, pair, pair, 0.5, 6657, 128, p, p, p, p, None) == -2      # the looped form's 60 KiB
+    assert L._fn["amid_itc_mix_fwd_f32"](p, p, pair, pair, pair, pair, 0.5, 8, 126, p, p, p, p, None) == -1         # D % 4

@@ -1,5 +1,6 @@
 """GPU parity of the whole SASRec path (forward, loss, backward, optimizer, graph replay) against
 the CPU oracle and the reference-generated golden vectors.  Everything runs through libamid_hip.so."""
+import copy
 import os
 
 import numpy as np
@@ -697,6 +698,178 @@ def test_dr_two_optimizers_track_oracle():
             Dd = v.numel() // 3
             d = torch.cat((d[:Dd], d[2 * Dd:]))
         assert float(d.max()) < 3e-4, (k, float(d.max()))
+
+
+# ---------------------------------------------------------------------------- the comp modules at the batch sizes run.sh trains
+def pick_open_threshold(softmaxes, B):
+    """The threshold midway across the gap of the oracle's batch-softmax values with the largest margin / threshold, among the gaps that leave
+    between B / 8 and 7 B / 8 gates open in every one of `softmaxes` (each the values of one of the modules that share the threshold); the
+    margin is the distance from the threshold to the nearest value of any of them.  Returns (threshold, margin / threshold)."""
+    sms = [s.double().reshape(-1) for s in softmaxes]
+    vals = torch.cat(sms).sort().values
+    best, best_t = -1.0, None
+    for t in ((vals[1:] + vals[:-1]) / 2).tolist():
+        if all(B <= 8 * int((s > t).sum()) <= 7 * B for s in sms):
+            r = min(float((s - t).abs().min()) for s in sms) / t
+            if r > best:
+                best, best_t = r, t
+    assert best_t is not None
+    return float(best_t), best
+
+
+def comp_case(variant, D, hid, T, B, seed, n_items=3000):
+    """Parameters and a train batch as tests/test_gpu_eval_variants.py:oracle_case builds them: last-LayerNorm weights x 0.5 (itc) / table x 0.35
+    (inc), so that the batch softmax is neither flat nor one-hot; no pad positions, so the pair-max scores are distinct."""
+    itc, inc, dr = variant.startswith("itc"), variant.startswith("inc"), variant.endswith("+dr")
+    P = orc.random_params(orc.sasrec_param_shapes(n_items, D, T, hid, itc_bs=B if itc else 0, dr=dr, inc_bs=B if inc else 0), seed=seed)
+    if itc:
+        for d in (1, 2):
+            P[f"sac{d}.last_layernorm.weight"] *= 0.5
+    if inc:
+        P["item_emb_layer.emb_item.weight"] *= 0.35
+    g = torch.Generator().manual_seed(seed + 1)
+    batch = orc.synthetic_batch(B, T, n_items - 1, pad_id=n_items - 1, neg=1, seed=seed + 2)
+    batch["seq_d1"] = torch.randint(1, n_items - 1, (B, T), generator=g)
+    batch["seq_d2"] = torch.randint(1, n_items - 1, (B, T), generator=g)
+    if dr:
+        batch["ob_label"] = (torch.rand(B, generator=g) < 0.6).long()
+    return P, batch
+
+
+COMP_CASES = [("itc", 64, 16, 20, 32, False), ("itc", 128, 32, 20, 33, True), ("itc", 64, 16, 20, 48, True), ("itc", 128, 32, 20, 256, False),
+              ("itc", 128, 32, 20, 257, False), ("itc+dr", 128, 32, 20, 256, False), ("inc", 64, 16, 20, 48, True), ("inc", 128, 32, 20, 256, False)]
+
+
+@pytest.mark.parametrize("variant,D,hid,T,B,train", COMP_CASES)
+def test_comp_gradients_vs_oracle_at_trained_batch_sizes(variant, D, hid, T, B, train):
+    """Forward, loss and every gradient against the oracle at the batches on which InterComp's mix runs its 512-thread kernels (32 <= B <= 256, D
+    64 / 128; 257: its looped form with several rows per workgroup) -- the last case is what run.sh trains -- with a threshold that opens between
+    an eighth and seven eighths of the gates, chosen from the oracle's own softmax values (with the dropout masks where dropout is on) and
+    at least 1 % of its value away from each of them.  The bars are those of the batch-of-8 tests above."""
+    from amid_amd.engine import SasrecEngine
+    itc, dr = variant.startswith("itc"), variant.endswith("+dr")
+    mods = ("itc_d1", "itc_d2") if itc else ("inc_d1", "inc_d2")
+    tkey = "threshold2" if itc else "threshold1"
+    P, batch = comp_case(variant, D, hid, T, B, seed=60 + D)
+    seed, step = 35, 2
+    masks = orc.philox_masks_sasrec(B, T if itc else 2 * T, D, seed=seed, step=step) if train else None
+    kw = dict(isItC=True) if itc else dict(isInC=True)
+    taps = {}
+    with torch.no_grad():                                        # the softmax values do not depend on the threshold
+        orc.sasrec_forward(P, batch["i_node"], batch["neg_samples"], batch["seq_d1"], batch["seq_d2"], masks, taps, isDR=dr, **kw)
+    ts, ratio = pick_open_threshold([taps[m]["softmax"] for m in mods], B)
+    gates = [taps[m]["softmax"] > ts for m in mods]
+    tag = f"comp {variant} D={D} B={B} train={train}"
+    log(f"{tag}: threshold {ts:.6e} margin / threshold {ratio:.3e} open {[int(g.sum()) for g in gates]}")
+    assert ratio >= 1e-2, ratio
+    kw[tkey] = ts
+    ekw = dict(itc_bs=B, itc_threshold=ts) if itc else dict(inc_bs=B, inc_threshold=ts)
+    eng = SasrecEngine(3000, D, T, hid, lr=1e-3, seed=seed, dr=dr, **ekw)
+    eng.load_state_dict(P)
+    if dr:
+        info, outs, grads = orc.dr_loss_and_grads(P, batch, "e", masks, dr_e_w=0.1, **kw)
+        eng.dr_mode = 0
+        pl = eng.plan(B, T, 2, need_grad=True)
+        eng.set_step(step, seed)
+        cu = {k: v.cuda() for k, v in batch.items()}
+        eng.load_batch(pl, cu["i_node"], cu["neg_samples"], cu["seq_d1"], cu["seq_d2"], cu["label"], cu["domain_id"], cu["ob_label"])
+        eng.enqueue_prepare(pl, sparse=True)
+        eng.enqueue_forward(pl, train=train, with_loss=True)
+        eng.enqueue_backward(pl, train=train)
+        eng.sync()
+        eng.check_index_error(pl)
+        assert torch.equal(pl.itc_gate.cpu(), gates[0].float())
+        for name, got, want in zip(("p1", "p2", "ips1", "ips2", "g1", "g2"), (pl.p1, pl.p2, pl.ips1, pl.ips2, pl.g1, pl.g2), outs):
+            e = relmax(got, want)
+            log(f"{tag} {name} relmax {e:.3e}")
+            assert e < 3e-5, (name, e)
+        lc, le, _ = (float(v) for v in pl.dr_losses.cpu())
+        log(f"{tag} loss_cls {lc:.7f} (oracle {float(info['loss_cls']):.7f}) loss_dr_e {le:.7f} (oracle {float(info['loss_dr_e']):.7f})")
+        assert abs(lc + 0.1 * le - float(info["loss"])) < 1e-5
+        dr_grads_check(tag, eng, pl, grads, 5e-4)
+        return
+    loss, (p1, p2), grads = orc.loss_and_grads("sasrec", P, batch, masks, **kw)
+    pl = run_forward(eng, batch, train=train, with_loss=True, step=step, seed=seed)
+    if itc:
+        assert torch.equal(pl.itc_gate.cpu(), gates[0].float())
+    else:
+        for d in (0, 1):
+            assert torch.equal(pl.inc_gate[d].cpu(), gates[d].float())
+    e1, e2 = relmax(pl.p1, p1), relmax(pl.p2, p2)
+    log(f"{tag} p1 relmax {e1:.3e} p2 relmax {e2:.3e}")
+    assert e1 < 3e-5 and e2 < 3e-5
+    eng.enqueue_backward(pl, train=train)
+    eng.sync()
+    assert abs(float(pl.loss.item()) - float(loss)) < 1e-5
+    grads_check(tag, eng, pl, grads, 5e-4 if train else 2e-4, 5e-3 if train else 2e-4)
+
+
+def test_itc_train_step_vs_oracle_dense_adam():
+    """Three isItC train steps (dropout on) at a batch of 48 -- the mix's 512-thread forward and backward -- against the oracle's dense Adam:
+    losses and the parameters after the steps, InterComp's included; eager and graph replay bit-identical.  The pair-max scores move with every
+    step's dropout masks, so the threshold is one that keeps 1 % of its value from the oracle's softmax values of all three steps."""
+    D, T, B, hid = 64, 20, 48, 16
+    P, batch = comp_case("itc", D, hid, T, B, seed=60 + D)
+    seed, lr = 5, 1e-3
+
+    # A step's softmax values depend on the threshold only through the gates of the steps before it.  So the threshold is narrowed step by
+    # step: (lo, hi) holds no softmax value of the steps so far -- any threshold in it gives them the same gates --, the next step's values
+    # split it, and the parts that keep 1 % of their midpoint on either side and open an eighth to seven eighths of that step's gates are
+    # tried widest first; a part that leaves a later step no such part is dropped for the next one.
+    def narrow(Pref, opt, t, lo, hi):
+        if t == 4:
+            return Pref, (lo + hi) / 2, [], []
+        masks = orc.philox_masks_sasrec(B, T, D, seed=seed, step=t)
+        taps = {}
+        with torch.no_grad():
+            orc.sasrec_forward(Pref, batch["i_node"], batch["neg_samples"], batch["seq_d1"], batch["seq_d2"], masks, taps, isItC=True)
+        sm = torch.cat((taps["itc_d1"]["softmax"], taps["itc_d2"]["softmax"])).double()      # (both directions' values, equal up to rounding)
+        edges = [lo] + sorted(v for v in sm.tolist() if lo < v < hi) + [hi]
+        parts = [(a, b) for a, b in zip(edges[:-1], edges[1:])
+                 if (b - a) / (b + a) >= 1e-2 and 2 * B <= 8 * int((sm > (a + b) / 2).sum()) <= 2 * 7 * B]
+        for a, b in sorted(parts, key=lambda p: (p[1] - p[0]) / (p[1] + p[0]), reverse=True):
+            Pn, on = {k: v.clone() for k, v in Pref.items()}, copy.deepcopy(opt)
+            loss = orc.train_step("sasrec", Pn, on, batch, masks, isItC=True, threshold2=(a + b) / 2)
+            r = narrow(Pn, on, t + 1, a, b)
+            if r is not None:
+                return r[0], r[1], [loss] + r[2], [sm] + r[3]
+        return None
+
+    P0 = {k: v.clone() for k, v in P.items()}
+    found = narrow(P0, orc.DenseAdam(P0, lr=lr), 1, 0.0, 1.0)
+    assert found is not None
+    Pref, ts, ref_losses, sms = found
+    ratio = min(float((s - ts).abs().min()) for s in sms) / ts
+    n_open = [int((s > ts).sum()) // 2 for s in sms]
+    log(f"itc dense-adam B={B}: threshold {ts:.6e} margin / threshold {ratio:.3e} open {n_open}")
+    assert ratio >= 1e-2 and all(B <= 8 * n <= 7 * B for n in n_open)
+
+    def run(use_graph):
+        eng = make_itc_engine(P, T, B, ts, lr=lr, seed=seed)
+        pl = eng.plan(B, T, 2, need_grad=True)
+        cu = {k: v.cuda() for k, v in batch.items()}
+        eng.load_batch(pl, cu["i_node"], cu["neg_samples"], cu["seq_d1"], cu["seq_d2"], cu["label"], cu["domain_id"])
+        if use_graph:
+            eng.capture_train_step(pl)
+        losses = []
+        for _ in range(3):
+            eng.replay_train_step(pl) if use_graph else eng.enqueue_train_step(pl)
+            eng.sync()
+            losses.append(float(pl.loss.item()))
+        eng.flush_table(); eng.sync()
+        return losses, {k: v.cpu().clone() for k, v in eng.state_dict().items()}
+    l0, s0 = run(False)
+    l1, s1 = run(True)
+    assert l0 == l1 and all(torch.equal(s0[k], s1[k]) for k in s0)
+    for a, b in zip(l0, ref_losses):
+        assert abs(a - float(b)) < 2e-5
+    for k, v in Pref.items():
+        d = (s0[k] - v).abs()
+        if k.endswith("in_proj_bias"):
+            Dd = v.numel() // 3
+            d = torch.cat((d[:Dd], d[2 * Dd:]))      # chaotic key-bias slice, see test_oracle_golden
+        log(f"itc dense-adam B={B} {k:50s} max |diff| {float(d.max()):.3e}")
+        assert float(d.max()) < 2e-4, (k, float(d.max()))
 
 
 # ---------------------------------------------------------------------------- edge shapes (SURVEY.md section 8(c): ragged / empty / maximum inputs)
