@@ -461,6 +461,33 @@ static int fr_topk_launch(FrArgs a, hipStream_t st) {
     return AMID_OK;
 }
 
+// fr_topk_launch cut where it stops depending on the user: the item halves alone (frozen weights: once for every batch of a dataset) ...
+template <int HID>
+static int fr_topk_items_launch(FrArgs a, hipStream_t st) {
+    static unsigned long long done_items = 0;
+    const int n_t = a.n_tiles[0] + a.n_tiles[1];
+    if (int rc = lds_attr_once((const void*)fr_items_kernel<HID>, 160 * 1024, done_items)) return rc;
+    fr_items_kernel<HID><<<std::min(n_t, FR_GRID), FR_THREADS, (size_t)a.D * (HID + 1) * 4, st>>>(a);
+    AMID_LAUNCH_CHECK();
+    return AMID_OK;
+}
+
+// ... and the rest, reading the ci region an earlier fr_topk_items_launch filled (the same kernels on the same operands as fr_topk_launch:
+// fr_user_kernel and fr_items_kernel write disjoint regions and read nothing of each other)
+template <int HID>
+static int fr_topk_users_launch(FrArgs a, hipStream_t st) {
+    static unsigned long long done_topk = 0, done_merge = 0;
+    fr_user_kernel<HID><<<a.B, FR_THREADS, 0, st>>>(a);
+    AMID_LAUNCH_CHECK();
+    if (int rc = lds_attr_once((const void*)fr_topk_kernel<HID>, 160 * 1024, done_topk)) return rc;
+    fr_topk_kernel<HID><<<dim3((a.B + FR_UB - 1) / FR_UB, a.n_ranges), FR_THREADS, fr_topk_lds_bytes(a.K), st>>>(a);
+    AMID_LAUNCH_CHECK();
+    if (int rc = lds_attr_once((const void*)fr_merge_kernel, 160 * 1024, done_merge)) return rc;
+    fr_merge_kernel<<<a.B, FR_THREADS, fr_merge_lds_bytes(a.K), st>>>(a);
+    AMID_LAUNCH_CHECK();
+    return AMID_OK;
+}
+
 }  // namespace amid
 
 using namespace amid;
@@ -503,4 +530,36 @@ extern "C" int amid_topk_f32(const float* u, long long u_dom_stride, const long 
     a.exclude = exclude_history ? 1 : 0; a.out_ids = ids; a.out_s = scores;
     const hipStream_t st = (hipStream_t)stream;
     return hid == 16 ? fr_topk_launch<16>(a, st) : hid == 32 ? fr_topk_launch<32>(a, st) : fr_topk_launch<64>(a, st);
+}
+
+// amid_topk_f32 as two calls (a dataset's batches against frozen weights: the item halves once, the rest per batch).  Both carve the
+// workspace as amid_topk_f32 does for (B, n_pool_d1, n_pool_d2, hid, k >= 1); where the ci region starts depends on B and hid only.
+extern "C" int amid_topk_items_f32(int B, const long long* pool_d1, int n_pool_d1, const long long* pool_d2, int n_pool_d2, const float* table,
+                                   long long n_rows, const float* w1, int D, int hid, void* workspace, int* flags, void* stream) {
+    AMID_CHECK_ARG(pool_d1 && pool_d2 && table && w1 && workspace && flags);
+    AMID_CHECK_ARG(B >= 1 && n_pool_d1 >= 1 && n_pool_d2 >= 1 && n_rows >= 1 && n_rows <= 0x7fffffffLL);
+    if (!fr_shape_ok(D, hid)) return AMID_ERR_UNSUPPORTED;
+    FrArgs a;
+    fr_fill(a, nullptr, 0, nullptr, B, pool_d1, n_pool_d1, pool_d2, n_pool_d2, nullptr, nullptr, nullptr, table, n_rows, w1, nullptr, nullptr,
+            nullptr, D, hid, 1, workspace, flags);
+    const hipStream_t st = (hipStream_t)stream;
+    return hid == 16 ? fr_topk_items_launch<16>(a, st) : hid == 32 ? fr_topk_items_launch<32>(a, st) : fr_topk_items_launch<64>(a, st);
+}
+
+extern "C" int amid_topk_users_f32(const float* u, long long u_dom_stride, const long long* domain_id, int B, const long long* pool_d1,
+                                   int n_pool_d1, const long long* pool_d2, int n_pool_d2, const long long* own_items, const int* own_off,
+                                   const int* rows, const float* table, long long n_rows, const float* w1, const float* b1, const float* w2,
+                                   const float* b2, int D, int hid, int k, int exclude_history, void* workspace, int* flags, long long* ids,
+                                   float* scores, void* stream) {
+    AMID_CHECK_ARG(u && domain_id && pool_d1 && pool_d2 && table && w1 && b1 && w2 && b2 && workspace && flags && ids && scores);
+    AMID_CHECK_ARG(k >= 1 && k <= 256);
+    AMID_CHECK_ARG(B >= 1 && n_pool_d1 >= 1 && n_pool_d2 >= 1 && n_rows >= 1 && n_rows <= 0x7fffffffLL && u_dom_stride >= 0);
+    AMID_CHECK_ARG(!exclude_history || own_items == nullptr || (own_off && rows));
+    if (!fr_shape_ok(D, hid)) return AMID_ERR_UNSUPPORTED;
+    FrArgs a;
+    fr_fill(a, u, u_dom_stride, domain_id, B, pool_d1, n_pool_d1, pool_d2, n_pool_d2, exclude_history ? own_items : nullptr, own_off, rows,
+            table, n_rows, w1, b1, w2, b2, D, hid, k, workspace, flags);
+    a.exclude = exclude_history ? 1 : 0; a.out_ids = ids; a.out_s = scores;
+    const hipStream_t st = (hipStream_t)stream;
+    return hid == 16 ? fr_topk_users_launch<16>(a, st) : hid == 32 ? fr_topk_users_launch<32>(a, st) : fr_topk_users_launch<64>(a, st);
 }

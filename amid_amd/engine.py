@@ -27,6 +27,7 @@ from ._lib import lib, ptr_array
 from .engine_dp import DataParallelMixin, HipMergeBackend      # noqa: F401  (re-exported)
 from .engine_graph import GraphMixin
 from .engine_io import InputMixin
+from .engine_topk import TopkMixin
 from .plan import (DR_HEADS, SASREC_HEADS, SASREC_LN_EPS, SASREC_P_DROP, FlatParams, SasrecPlan, Shape,      # noqa: F401  (re-exported)
                    sasrec_dense_names)
 
@@ -42,7 +43,7 @@ QKV_FAMILIES = tuple(n for n, _ in SASREC_FAMILIES[:4])
 FFN_FAMILIES = tuple(n for n, _ in SASREC_FAMILIES[4:])
 
 
-class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
+class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
     """Parameters, optimizer state and launch sequences for SASRec (isInC = isItC = isDR = False)."""
 
     HEADS = SASREC_HEADS
@@ -1644,11 +1645,12 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin):
     # The user vectors come from the launches the sampled evaluation runs for this model (enqueue_eval's own-domain pl.ev_u -- for isItC
     # the mixed vector --, enqueue_forward's pl.u where eval_fused_ok says no), so the full-catalog scores are the bits test() would give the
     # same candidates.
-    def enqueue_user_vectors(self, pl: SasrecPlan, fix_value: float = 0.0):
+    def enqueue_user_vectors(self, pl: SasrecPlan, fix_value: float = 0.0, build_images: bool = True):
         """The user vectors of the batch loaded into `pl` (load_batch with labels and domain ids), on the engine's stream.  Returns
-        (tensor, dom_stride): user b's vector starts dom_stride * domain[b] + b * D floats into the tensor."""
+        (tensor, dom_stride): user b's vector starts dom_stride * domain[b] + b * D floats into the tensor.  build_images=False: the
+        fused evaluation's weight images are current (topk_epoch builds them once for all its batches, as eval_epoch does)."""
         if self.eval_fused_ok(pl):
-            self.enqueue_eval(pl, fix_value, with_loss=False, want_scores=True)
+            self.enqueue_eval(pl, fix_value, with_loss=False, want_scores=True, build_images=build_images)
             return pl.ev_u, 0
         self.enqueue_prepare(pl, sparse=False)
         self.enqueue_forward(pl, train=False, with_loss=False)

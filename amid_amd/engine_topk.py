@@ -1,0 +1,133 @@
+"""Top-K for a whole dataset (split out of engine.py): the batches of an epoch resident in HBM against frozen weights, one graph replay a
+batch.  What SasrecEngine.enqueue_topk does per call is cut where it stops depending on the user (csrc/full_rank.hip
+amid_topk_items_f32 / amid_topk_users_f32), and the history sets come from the plan's static sequences on the device
+(csrc/own_sets.hip amid_own_from_seq_i64) instead of a torch.sort + mask gather + cumsum whose shape depends on the data."""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from ._lib import lib
+
+from .plan import SasrecPlan
+
+
+class TopkMixin:
+    def _topk_buffers(self, pl: SasrecPlan, k: int):
+        """The plan's own-set buffers (own [B T] int64, own_off [B + 1], scratch counts [B], rows 0 .. B - 1: int32) and its static
+        result buffers for this k (ids [B, k] int64, scores [B, k]); allocated once."""
+        B, T = pl.shape.B, pl.shape.T
+        fresh = False
+        if not hasattr(pl, "tk_own"):
+            dev = self.device
+            pl.tk_own = torch.zeros(B * T, dtype=torch.int64, device=dev)
+            pl.tk_own_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+            pl.tk_cnt = torch.zeros(B, dtype=torch.int32, device=dev)
+            pl.tk_rows = torch.arange(B, dtype=torch.int32, device=dev)
+            pl.tk_out = {}
+            fresh = True
+        if k not in pl.tk_out:
+            pl.tk_out[k] = (torch.zeros(B, k, dtype=torch.int64, device=self.device), torch.zeros(B, k, dtype=torch.float32, device=self.device))
+            fresh = True
+        if fresh:
+            torch.cuda.synchronize(self.device)
+        return pl.tk_out[k]
+
+    def enqueue_topk_items(self, pl: SasrecPlan, pools, k: int) -> None:
+        """The item halves of both pools' candidates into the engine's top-K workspace, for the weights as they are now: one launch
+        (amid_topk_items_f32).  enqueue_topk_batch reads them until the workspace, the pools or the weights change."""
+        B = pl.shape.B
+        p1, p2 = pools
+        ws = self._full_rank_workspace(B, p1.numel(), p2.numel(), int(k))
+        lib().call("amid_topk_items_f32", B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel(), self.table.data_ptr(), self.n_rows,
+                   self._scorer()["w1"], self.D, self.hid, ws.data_ptr(), pl.err.data_ptr(), self.s)
+        self._tk_items = (ws.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel())
+
+    def enqueue_topk_batch(self, pl: SasrecPlan, pools, k: int, exclude_history: bool, ids: torch.Tensor, scores: torch.Tensor,
+                           build_images: bool = True) -> None:
+        """enqueue_topk for the batch in the plan's static inputs, without its items launch and without a host-built history set: the
+        user vectors (enqueue_user_vectors: the launches recommend() uses, so the same bits), with exclude_history the rows' own sets from
+        pl.in_seq_d1 / pl.in_seq_d2 / pl.domain (amid_own_from_seq_i64: two launches), amid_topk_users_f32 (three) on the item halves
+        enqueue_topk_items left in the workspace for these pools.  ids [B, k] int64, scores [B, k].  Fixed shapes, no host read, no
+        allocation once _topk_buffers has run: capturable."""
+        L, s, shp = lib(), self.s, pl.shape
+        B = shp.B
+        p1, p2 = pools
+        self._topk_buffers(pl, int(k))
+        ws = self._full_rank_workspace(B, p1.numel(), p2.numel(), int(k))
+        if getattr(self, "_tk_items", None) != (ws.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel()):
+            raise ValueError("enqueue_topk_batch: the workspace holds no item halves for these pools and this batch size (enqueue_topk_items)")
+        u, stride = self.enqueue_user_vectors(pl, build_images=build_images)
+        if exclude_history:
+            L.call("amid_own_from_seq_i64", pl.in_seq_d1.data_ptr(), pl.in_seq_d2.data_ptr(), pl.domain.data_ptr(), B, shp.T,
+                   pl.tk_cnt.data_ptr(), pl.tk_own.data_ptr(), pl.tk_own_off.data_ptr(), s)
+        L.call("amid_topk_users_f32", u.data_ptr(), stride, pl.domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel(),
+               pl.tk_own.data_ptr(), pl.tk_own_off.data_ptr(), pl.tk_rows.data_ptr(), self.table.data_ptr(), self.n_rows,
+               *self._scorer().values(), self.D, self.hid, int(k), 1 if exclude_history else 0, ws.data_ptr(), pl.err.data_ptr(),
+               ids.data_ptr(), scores.data_ptr(), s)
+
+    def capture_topk(self, pl: SasrecPlan, pools, k: int, exclude_history: bool) -> None:
+        """enqueue_topk_batch as a hipGraph over the plan's static inputs and result buffers, after enqueue_topk_items for these pools.
+        One stream, no parallel branch.  Parameters, the item halves and the weight images are read at replay time (topk_epoch rebuilds the
+        latter two before its first replay), so the graph stays valid across train steps; the pools' and the workspace's addresses are baked
+        in (topk_epoch captures again when either moved).  Keyed by (k, exclude_history, pool sizes)."""
+        L = lib()
+        ids, scores = self._topk_buffers(pl, int(k))
+        self.enqueue_topk_batch(pl, pools, k, exclude_history, ids, scores)      # warm-up outside capture (LDS attributes, lazy buffers, images)
+        self.sync()
+        L.call("amid_graph_capture_begin", self.s)
+        try:
+            self.enqueue_topk_batch(pl, pools, k, exclude_history, ids, scores, build_images=False)
+        finally:
+            out = ctypes.c_void_p()
+            L.call("amid_graph_capture_end", self.s, ctypes.byref(out))
+        if not hasattr(pl, "topk_graphs"):
+            pl.topk_graphs = {}
+        p1, p2 = pools
+        key = (int(k), bool(exclude_history), p1.numel(), p2.numel())
+        old = pl.topk_graphs.get(key)
+        if old is not None:
+            L.call("amid_graph_destroy", old[0])
+        # (the pools are kept alive with the graph that reads them)
+        pl.topk_graphs[key] = (out.value, self._tk_items, (p1, p2))
+
+    def topk_epoch(self, pl: SasrecPlan, packed: torch.Tensor, pools, k: int, exclude_history: bool, use_graph: bool = True):
+        """Every batch of `packed` ([n, in_words] int64: pack_epoch's images with zero i_node and one zero negative per row, resident in
+        HBM) through the top-K launches: the lazy table flushed, the weight images and the pools' item halves built ONCE, then per batch
+        one device copy of the image into the plan's static inputs, one graph replay (use_graph=False: the same launches, eagerly) and
+        two device copies of the results out.  Returns (ids [n, B, k] int64, scores [n, B, k] float32) on the device; nothing is read back.
+        Where eval_fused_ok(pl) is false the user vectors are enqueue_prepare + enqueue_forward; that sequence is plain launches on the
+        engine's stream for an evaluation-mode batch on one GPU and is captured like the fused one."""
+        if packed.dtype != torch.int64 or packed.dim() != 2 or packed.shape[1] != pl.in_words:
+            raise ValueError(f"topk_epoch takes [n, {pl.in_words}] int64 batch images (pack_epoch)")
+        if self.table_m is not None:
+            self.flush_table()                   # rows with pending zero-gradient Adam steps must be current
+        L, k = lib(), int(k)
+        n, B = packed.shape[0], pl.shape.B
+        p1, p2 = pools
+        ids = torch.empty(n, B, k, dtype=torch.int64, device=self.device)
+        scores = torch.empty(n, B, k, dtype=torch.float32, device=self.device)
+        b_ids, b_scores = self._topk_buffers(pl, k)
+        fused = self.eval_fused_ok(pl)
+        with torch.cuda.stream(self.stream):
+            if fused:
+                self._enqueue_eval_images(pl)        # this epoch's weight images, once (the batches' launches only read them)
+            self.enqueue_topk_items(pl, pools, k)
+        key = (k, bool(exclude_history), p1.numel(), p2.numel())
+        if use_graph:
+            ent = getattr(pl, "topk_graphs", {}).get(key)
+            if ent is None or ent[1] != self._tk_items:
+                with torch.cuda.stream(self.stream):
+                    pl.in_pack.copy_(packed[0], non_blocking=True)
+                self.capture_topk(pl, pools, k, exclude_history)
+        with torch.cuda.stream(self.stream):
+            for i in range(n):
+                pl.in_pack.copy_(packed[i], non_blocking=True)
+                if use_graph:
+                    L.call("amid_graph_launch", pl.topk_graphs[key][0], self.s)
+                else:
+                    self.enqueue_topk_batch(pl, pools, k, exclude_history, b_ids, b_scores, build_images=False)
+                ids[i].copy_(b_ids, non_blocking=True)
+                scores[i].copy_(b_scores, non_blocking=True)
+        return ids, scores

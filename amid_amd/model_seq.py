@@ -405,6 +405,62 @@ class SASRec(nn.Module):
         eng.check_index_error(pl)
         return ids, scores
 
+    def _candidate_pools(self, pool):
+        """recommend()'s `pool` argument as (domain 0's, domain 1's) sorted unique int64 device tensors.  The whole table (None) is one
+        tensor for the life of the model, and a pool that is already such a tensor is passed through, so that recommend_all's captured
+        graphs, which hold the pools' addresses, survive from call to call."""
+        eng = self.engine
+        dev = eng.device
+        if pool is None:
+            if getattr(self, "_all_rows", None) is None:
+                self._all_rows = torch.arange(eng.n_rows, dtype=torch.int64, device=dev)
+            return (self._all_rows, self._all_rows)
+
+        def one(q):
+            if isinstance(q, torch.Tensor) and q.device == dev and q.dtype == torch.int64 and q.dim() == 1 and q.is_contiguous() \
+                    and (q.numel() < 2 or bool((q[1:] > q[:-1]).all())):
+                return q
+            return torch.unique(torch.as_tensor(q).to(dev, torch.int64))
+        if isinstance(pool, (tuple, list)):
+            pools = tuple(one(q) for q in pool)
+            if len(pools) != 2:
+                raise ValueError("recommend_all: pool is None, one tensor of item ids, or a pair (domain 0's, domain 1's)")
+            return pools
+        p = one(pool)
+        return (p, p)
+
+    @torch.no_grad()
+    def recommend_all(self, users: Dict[str, torch.Tensor], k: int = 10, pool=None, exclude_history: bool = True, use_graph: bool = True):
+        """recommend() for every batch of a dataset: users = {"seq_d1", "seq_d2": [n, B, T], "domain_id": [n, B]} (what
+        DeviceBatches.epoch_tensors() gives fits; other keys are ignored), pool / k / exclude_history as in recommend().  Returns
+        (ids [n, B, k] int64, scores [n, B, k] float32) on the device: batch i's rows are recommend()'s for the same batch, bit for bit
+        (ordering, ties to the lower id, -1 / -inf padding).  The weights do not change inside the call, so the candidates' item halves
+        are formed once, the history sets come from the sequences on the device, and a batch is one device copy of its packed image and
+        one graph replay (SasrecEngine.topk_epoch; use_graph=False: the same launches, eagerly)."""
+        eng = self.engine
+        dev = eng.device
+        seq_d1 = torch.as_tensor(users["seq_d1"]).to(dev, torch.int64)
+        seq_d2 = torch.as_tensor(users["seq_d2"]).to(dev, torch.int64)
+        if seq_d1.dim() != 3 or seq_d1.shape != seq_d2.shape:
+            raise ValueError("recommend_all: seq_d1 and seq_d2 must be [n, B, T] tensors of one shape")
+        n, B, T = seq_d1.shape
+        dom = torch.as_tensor(users["domain_id"]).to(dev, torch.int64).reshape(n, B)
+        self._check_comp_batch(B)
+        if not 1 <= int(k) <= 256:
+            raise ValueError(f"k must be in 1..256, got {k}")
+        pools = self._candidate_pools(pool)
+        if min(int(q.numel()) for q in pools) < 1:
+            raise ValueError("recommend_all: an empty candidate pool")
+        pl = eng.plan(B, T, 2, need_grad=False)              # recommend()'s plan: the positive's slot and one negative, both zero
+        zero = torch.zeros(n, B, dtype=torch.int64, device=dev)
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        packed = eng.pack_epoch(pl, zero, zero.view(n, B, 1), seq_d1, seq_d2, torch.zeros(B, 2, device=dev), dom)
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        ids, scores = eng.topk_epoch(pl, packed, pools, int(k), bool(exclude_history), use_graph=use_graph)
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(pl)
+        return ids, scores
+
     def check_indices(self) -> None:
         """Raise IndexError if any batch since the last check carried an item id outside the table (nn.Embedding raises on the spot,
         model_seq.py:27-29; the fused step flags it on the device and keeps going with row 0).  One device -> host read: call it

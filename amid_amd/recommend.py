@@ -1,0 +1,129 @@
+"""Top-K recommendations for every user of a CSV from saved weights (not in the reference, which only trains and evaluates).
+
+Takes the model flags of ``train_sr.py`` (``--model --emb_dim --hid_dim --seq_len --bs --isItC --isInC --ts1 --ts2 -ds -dm
+--overlap_ratio --data_root --device``; ``--isDR`` as in ``train_sr_dr.py``, here off unless given) and
+
+    --weights FILE          best_d1.pt / best_d2.pt / a model.state_dict() (loaded strictly), or a last.pt (its training state)
+    --users CSV             the rows to recommend for (default: the job's <dm>_test.csv)
+    --topk K                1 .. 256
+    --pool {dataset,table}  candidates: the two item pools of the job's training CSV, or every row of the table
+    --history {eval,full}   eval: the rows as test() sees them (the last own-domain item held out as the positive);
+                            full: that item appended again -- the recommendation after the whole history
+    --out FILE.npz          user_id [N], domain_id [N], items [N, K] (CSV item ids, -1 where a pool ran out), scores [N, K], in CSV row order
+    --metrics               also evaluate these weights with test() on the same CSV (sampled negatives, drop_last), printed and returned
+
+    python recommend.py --data_root /path/to/AMID -ds amazon -dm cloth_sport --overlap_ratio 0.75 --model sasrec --bs 256 \
+        --seq_len 50 --emb_dim 128 --weights runs/seed0/best_d1.pt --topk 10 --out cloth_sport_top10.npz
+
+Every row of the CSV gets a recommendation: the last batch is filled with rows from the start of the CSV (comp models need whole
+``--bs``-row batches) and the surplus is cut off.  The ranking is ``SASRec.recommend_all``: one graph replay a batch.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from . import train_sr as base
+from .dataset_seq import DeviceBatches, DualDomainSeqDataset
+from .model_seq import BERT4Rec, SASRec
+
+
+def build_parser():
+    p = base.build_parser()
+    p.description = "Top-K recommendations from saved weights"
+    p.add_argument("--isDR", type=bool, default=False, help="the weights are a doubly-robust model's (train_sr_dr.py)")
+    p.add_argument("--weights", type=str, required=True, help="best_d1.pt / best_d2.pt / a state_dict, or a last.pt")
+    p.add_argument("--users", type=str, default=None, help="CSV of the rows to recommend for (default: <data_root>/<ds>_dataset/<dm>_test.csv)")
+    p.add_argument("--topk", type=int, default=10)
+    p.add_argument("--pool", type=str, default="dataset", choices=("dataset", "table"))
+    p.add_argument("--history", type=str, default="eval", choices=("eval", "full"))
+    p.add_argument("--out", type=str, default="recommendations.npz")
+    p.add_argument("--metrics", action="store_true", help="also run test() on the CSV with these weights")
+    return p
+
+
+def full_history(seq_d1: np.ndarray, seq_d2: np.ndarray, i_node: np.ndarray, domain_id: np.ndarray):
+    """--history full: every row's held-out item behind its own-domain sequence, the sequence shifted left by one (its oldest entry,
+    a pad id where the history is short, drops out); the other domain's sequence is unchanged.  [N, T] int64 arrays in, copies out."""
+    s1, s2 = seq_d1.copy(), seq_d2.copy()
+    for s, rows in ((s1, domain_id == 0), (s2, domain_id != 0)):
+        s[rows, :-1] = s[rows, 1:]
+        s[rows, -1] = i_node[rows]
+    return s1, s2
+
+
+def filled_batches(n_rows: int, bs: int) -> np.ndarray:
+    """Row indices [n_batches, bs] covering 0 .. n_rows - 1 in order; the last batch's tail is rows from the start again."""
+    nb = (n_rows + bs - 1) // bs
+    return (np.arange(nb * bs) % n_rows).reshape(nb, bs)
+
+
+def load_weights(model, path: str) -> str:
+    """Load `path` into the model; returns what it was ("training state" / "state dict")."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(ck, dict) and "format" in ck and "engine" in ck:
+        model.load_training_state(ck)
+        return "training state"
+    model.load_state_dict(ck, strict=True)
+    return "state dict"
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if "+" in args.domain_type:
+        raise SystemExit(f"recommend.py with a joint job (-dm {args.domain_type}) is not supported: recommend for one dataset per run")
+    if not 1 <= args.topk <= 256:
+        raise SystemExit(f"--topk must be in 1..256, got {args.topk}")
+    cls = {"sasrec": SASRec, "bert4rec": BERT4Rec}.get(args.model.lower())
+    if cls is None:
+        raise SystemExit(f"unknown --model {args.model!r} (sasrec | bert4rec)")
+    user_length, item_length = 895510, 447410                                             # train_sr.py:447, :450
+    root = os.path.join(args.data_root, f"{args.dataset_type}_dataset")
+    users_csv = args.users or os.path.join(root, f"{args.domain_type}_test.csv")
+    ds = DualDomainSeqDataset(seq_len=args.seq_len, isTrain=False, neg_nums=args.neg_nums, long_length=args.long_length,
+                              pad_id=item_length + 1, seed=1000, csv_path=users_csv)
+    if len(ds) < 1:
+        raise SystemExit(f"{users_csv}: no rows")
+    torch.cuda.set_device(torch.device(args.device))
+    model = cls(user_length=2 * user_length, user_emb_dim=args.emb_dim, item_length=2 * item_length, item_emb_dim=args.emb_dim,
+                seq_len=args.seq_len, hid_dim=args.hid_dim, bs=args.bs, isInC=args.isInC, isItC=args.isItC, threshold1=args.ts1,
+                threshold2=args.ts2, isDR=bool(args.isDR), seed=0)
+    kind = load_weights(model, args.weights)
+    model.eval()
+    print(f"{args.weights}: {kind}; {len(ds)} rows of {users_csv}")
+    dev = torch.device(args.device)
+    pool = None
+    if args.pool == "dataset":
+        train_csv = os.path.join(root, f"{args.domain_type}_train{int(args.overlap_ratio * 100)}.csv")
+        ds_train = DualDomainSeqDataset(seq_len=args.seq_len, isTrain=True, neg_nums=1, long_length=args.long_length, pad_id=item_length + 1,
+                                        seed=0, csv_path=train_csv)
+        pool = tuple(torch.from_numpy(p).to(dev) for p in ds_train.pool)                  # sorted unique (dataset_seq.py:141-142)
+    s1, s2 = ds.seq_d1, ds.seq_d2
+    if args.history == "full":
+        s1, s2 = full_history(s1, s2, ds.i_node, ds.domain_id)
+    sel = filled_batches(len(ds), args.bs)
+    users = {"seq_d1": torch.from_numpy(s1[sel]).to(dev), "seq_d2": torch.from_numpy(s2[sel]).to(dev),
+             "domain_id": torch.from_numpy(ds.domain_id[sel]).to(dev)}
+    ids, scores = model.recommend_all(users, k=args.topk, pool=pool, exclude_history=True, use_graph=not args.no_graph)
+    N = len(ds)
+    out = {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy(),
+           "items": ids.reshape(-1, args.topk)[:N].cpu().numpy(), "scores": scores.reshape(-1, args.topk)[:N].cpu().numpy()}
+    if os.path.dirname(args.out):
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    np.savez(args.out, **out)
+    print(f"wrote {args.out}: top-{args.topk} of {N} rows ({sel.shape[0]} batches of {args.bs})")
+    out["metrics"] = None
+    if args.metrics:
+        val = DeviceBatches(ds, args.bs, shuffle=False, device=args.device, seed=0)
+        res = base.test(model, args, val)
+        names = ("HR@1", "NDCG@1", "HR@5", "NDCG@5", "HR@10", "NDCG@10", "MRR")
+        for key, sc in res.items():
+            print(f"val {key}: " + (f"{sc:.4f}" if key == "loss" else ", ".join(f"{n}: {v:.4f}" for n, v in zip(names, sc))))
+        out["metrics"] = res
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -1098,6 +1098,25 @@ int amid_topk_f32(const float* u, long long u_dom_stride, const long long* domai
                   const long long* pool_d2, int n_pool_d2, const long long* own_items, const int* own_off, const int* rows,
                   const float* table, long long n_rows, const float* w1, const float* b1, const float* w2, const float* b2, int D,
                   int hid, int k, int exclude_history, void* workspace, int* flags, long long* ids, float* scores, void* stream);
+/* amid_topk_f32 cut where it stops depending on the user, for the batches of a whole dataset against frozen weights:
+ * amid_topk_items_f32: the item halves W1[:, D:] table[c] of every candidate of both pools into the workspace's ci region (fr_items_kernel's
+ * launch alone; that region's place depends on B and hid only, so one call serves every k).
+ * amid_topk_users_f32: amid_topk_f32's arguments and results, reading a ci region that an earlier amid_topk_items_f32 filled for the same B,
+ * pools, table and w1 in the same workspace: the user halves, the per-range lists and the merge.  Items-then-users gives amid_topk_f32's ids
+ * and scores bit for bit (the same kernels on the same operands).  Error codes as amid_topk_f32, before any device call. */
+int amid_topk_items_f32(int B, const long long* pool_d1, int n_pool_d1, const long long* pool_d2, int n_pool_d2, const float* table,
+                        long long n_rows, const float* w1, int D, int hid, void* workspace, int* flags, void* stream);
+int amid_topk_users_f32(const float* u, long long u_dom_stride, const long long* domain_id, int B, const long long* pool_d1, int n_pool_d1,
+                        const long long* pool_d2, int n_pool_d2, const long long* own_items, const int* own_off, const int* rows,
+                        const float* table, long long n_rows, const float* w1, const float* b1, const float* w2, const float* b2, int D,
+                        int hid, int k, int exclude_history, void* workspace, int* flags, long long* ids, float* scores, void* stream);
+/* History sets from the sequences (csrc/own_sets.hip): own(b) = the sorted unique ids (signed order, the pad id kept) of row b's own-domain
+ * sequence, domain_id[b] != 0 ? seq_d2[b] : seq_d1[b] (seq_d1, seq_d2 [B, T], domain_id [B]), as the CSR list amid_topk_f32 reads with
+ * rows = 0 .. B - 1: own (capacity B * T; words past own_off[B] are not written), own_off [B + 1].  cnt: [B] ints of scratch.  Two launches on
+ * the stream, no host read, no allocation.  1 <= T <= 2048 (AMID_ERR_UNSUPPORTED above); null pointers, B <= 0, T <= 0 or B * T >= 2^31:
+ * AMID_ERR_ARG; both before any device call. */
+int amid_own_from_seq_i64(const long long* seq_d1, const long long* seq_d2, const long long* domain_id, int B, int T, int* cnt,
+                          long long* own, int* own_off, void* stream);
 
 /* ---- BERT4Rec strips on bf16 pieces (round 5; csrc/bert_strip.hip MODE 3) ------------------------------------------------------------------
  * The strip launches of a TransformerBlock (model_seq.py:242-245 and its autograd) with every product as six bf16 piece pairs at fp32
