@@ -23,8 +23,8 @@ are accepted and ignored; dropout follows ``module.training``.  Two ways to trai
   fused step       ``model.train_step(batch)`` = forward + masked BCE + backward + dense-equivalent lazy
                    Adam as one hipGraph replay -- what ``train_sr.py`` of this repo and ``bench.py`` use.
 
-Out of scope this round (constructors kept for import / state_dict parity, ``forward`` raises):
-GRU4Rec (recurrent), embUserLayerEnhance (dead code in the reference).  BERT4Rec(isInC=True) / (isItC=True) -- the comp module in
+Out of scope (constructor kept for import parity, ``forward`` raises): embUserLayerEnhance (dead code in the reference).  GRU4Rec is built
+in ``amid_amd.model_gru``; the ``GRU4Rec`` of this module is a stub that raises and names that class.  BERT4Rec(isInC=True) / (isItC=True) -- the comp module in
 FRONT of the encoders, model_seq.py:283-294 -- are built (the reference itself fails with both flags).
 SASRec(isItC=True, isDR=True) -- InterComp after the encoders + the doubly-robust heads, what run.sh trains through
 train_sr_dr.py -- IS built (csrc/intercomp.hip, amid_dr_loss_f32), and so is SASRec(isInC=True) -- InnerComp on the gathered rows
@@ -750,7 +750,8 @@ class GRU4Rec(nn.Module):
     def __init__(self, user_length, user_emb_dim, item_length, item_emb_dim, seq_len, hid_dim, bs, isInC, isItC, threshold1, threshold2,
                  isDR=False):                          # model_seq.py:58
         super().__init__()
-        _not_built("GRU4Rec (recurrent encoder, not the attention path)", "model_seq.py:56-113")
+        raise NotImplementedError("GRU4Rec is built in amid_amd.model_gru (class GRU4Rec, csrc/gru.hip): this constructor in model_seq is a stub "
+                                  "kept until its callers move over (model_seq.py:56-113; INTEGRATION.md section A)")
 
 
 class BERT4Rec(SASRec):

@@ -27,6 +27,7 @@ import torch
 
 from . import train_sr as base
 from .dataset_seq import DeviceBatches, DualDomainSeqDataset
+from .model_gru import GRU4Rec
 from .model_seq import BERT4Rec, SASRec
 
 
@@ -76,9 +77,9 @@ def main(argv=None):
         raise SystemExit(f"recommend.py with a joint job (-dm {args.domain_type}) is not supported: recommend for one dataset per run")
     if not 1 <= args.topk <= 256:
         raise SystemExit(f"--topk must be in 1..256, got {args.topk}")
-    cls = {"sasrec": SASRec, "bert4rec": BERT4Rec}.get(args.model.lower())
+    cls = {"gru4rec": GRU4Rec, "sasrec": SASRec, "bert4rec": BERT4Rec}.get(args.model.lower())
     if cls is None:
-        raise SystemExit(f"unknown --model {args.model!r} (sasrec | bert4rec)")
+        raise SystemExit(f"unknown --model {args.model!r} (gru4rec | sasrec | bert4rec)")
     user_length, item_length = 895510, 447410                                             # train_sr.py:447, :450
     root = os.path.join(args.data_root, f"{args.dataset_type}_dataset")
     users_csv = args.users or os.path.join(root, f"{args.domain_type}_test.csv")

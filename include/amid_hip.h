@@ -1182,6 +1182,37 @@ int amid_bert_strip_qkv_bwd_p3_f32(const float* dq, const float* dk, const float
                                    const void* step_state, int train, float p_drop, float* fdz, float* fdpre, float* fdx1, float* fdt,
                                    float* fd_o, float* fln_part, void* stream);
 
+/* ---- GRU4Rec's encoder (csrc/gru.hip) --------------------------------------------------------------------------------------------
+ * replaces: nn.GRU(D, D, 1, batch_first=True) of GRU4Rec.forward model_seq.py:72-73, :92-95 (h0 = 0; gate rows ordered r, z, n; all T
+ * positions are stepped through, pads included; the layer's dropout = 0.5 is a no-op with one layer) and its autograd.  D = 128 only.
+ * Activations are [2 B T, .] as everywhere: the rows of sequence (domain g, batch row b) are (g B + b) T + t.  w_ih / w_hh [3 D, D],
+ * b_ih / b_hh [3 D]: host arrays of two device pointers (domain 0, domain 1).
+ * live: NULL = all 2 B sequences; else amid_live_list_i32's list -- only sequence (domain[b], b) of every sample is processed and, where
+ * nothing else is said, no row of another sequence is read or written.  A workgroup takes 16 sequences of one domain; a sequence's
+ * results do not depend on its tile or slot (the same bits with and without a list, in the saving and the inference form).
+ * amid_gru_supported: 1 for D == 128, B, T > 0 and 2 B T 3 D floats within 32-bit byte offsets.  Null pointers and non-positive sizes:
+ * AMID_ERR_ARG; any other shape outside the supported ones: AMID_ERR_UNSUPPORTED -- both before anything touches a device.
+ *   amid_gru_proj_fwd_f32       gi = x W_ih^T + b_ih                                             [2 B T, 3 D]
+ *   amid_gru_rec_fwd_f32        the recurrence on gi: h [2 B T, D] and, for the backward, gates [2 B T, 3 D] = (r, z, n),
+ *                               ghn = W_hn h_{t-1} + b_hn and hprev = h_{t-1} (zeros at t = 0)    [2 B T, D] each
+ *   amid_gru_rec_fwd_infer_f32  the same kernel storing h only
+ *   amid_gru_rec_bwd_f32        the reverse walk under the cotangent dh on h: dgi (the gradient of gi) and dgh (of W_hh h + b_hh: dgi with
+ *                               the n block multiplied by r) [2 B T, 3 D].  zero_dead (with a list): the rows of dgi and dgh of the OTHER
+ *                               domain's sequence of every sample are zero-filled (a weight-gradient launch that walks every row reads
+ *                               exact zeros there); without it they are not touched and must not be read.
+ *   amid_gru_dx_f32             dx = dgi W_ih [2 B T, D]; zero_dead as above (the segment reduce of the table rows reads every row) */
+int amid_gru_supported(int B, int T, int D);
+int amid_gru_proj_fwd_f32(const float* x, const float* const* w_ih, const float* const* b_ih, int B, int T, int D, const int* live,
+                          float* gi, void* stream);
+int amid_gru_rec_fwd_f32(const float* gi, const float* const* w_hh, const float* const* b_hh, int B, int T, int D, const int* live,
+                         float* h, float* gates, float* ghn, float* hprev, void* stream);
+int amid_gru_rec_fwd_infer_f32(const float* gi, const float* const* w_hh, const float* const* b_hh, int B, int T, int D, const int* live,
+                               float* h, void* stream);
+int amid_gru_rec_bwd_f32(const float* dh, const float* gates, const float* ghn, const float* hprev, const float* const* w_hh, int B, int T,
+                         int D, const int* live, int zero_dead, float* dgi, float* dgh, void* stream);
+int amid_gru_dx_f32(const float* dgi, const float* const* w_ih, int B, int T, int D, const int* live, int zero_dead, float* dx,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
