@@ -1360,6 +1360,30 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
                self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(), ids.data_ptr(),
                nu.data_ptr(), cap, rows.data_ptr(), self.D, self.grad_scale, self.step_state.data_ptr(), s)
 
+    def enqueue_loop_optimizer(self, pl: SasrecPlan, g: torch.Tensor, sqnorm: Optional[torch.Tensor] = None, max_norm: float = float("inf")) -> None:
+        """The optimizer launch of the reference's own loop (amid_amd/optim.py): enqueue_optimizer's plain form reading the dense gradient
+        from `g` (a flat buffer laid out like self.dense.grad: the parameters' .grad tensors are its views) instead of the engine's own;
+        sqnorm (device scalar, enqueue_grad_sqnorm) + max_norm: the gradients clipped on the way (amid_optimizer_step_clip_f32)."""
+        self._ensure_opt_state()
+        if getattr(pl, "opt_done", False) or int(getattr(pl, "spans_owed", 0)):
+            raise RuntimeError("the plan's last backward was a fused train step's: its gradients are applied already")
+        fp = self.dense
+        args = (fp.data.data_ptr(), fp.m.data_ptr(), fp.v.data_ptr(), g.data_ptr(), fp.numel, self.table.data_ptr(), self.table_m.data_ptr(),
+                self.table_v.data_ptr(), self.table_last.data_ptr(), pl.uniq_ids.data_ptr(), pl.n_uniq.data_ptr(), self.n_sparse(pl),
+                pl.uniq_grad.data_ptr(), self.D, self.grad_scale, self.step_state.data_ptr())
+        if sqnorm is None:
+            lib().call("amid_optimizer_step_f32", *args, self.s)
+        else:
+            lib().call("amid_optimizer_step_clip_f32", *args, sqnorm.data_ptr(), float(max_norm), self.s)
+
+    def enqueue_grad_sqnorm(self, pl: SasrecPlan, g: torch.Tensor, out: torch.Tensor) -> None:
+        """out[0] = the squared 2-norm of the whole model's gradient: the flat dense gradient `g` and the plan's unique table rows."""
+        ws = getattr(self, "_sqnorm_ws", None)
+        if ws is None:
+            ws = self._sqnorm_ws = torch.empty(lib().value("amid_grad_sqnorm_workspace_bytes"), dtype=torch.uint8, device=self.device)
+        lib().call("amid_grad_sqnorm_f32", g.data_ptr(), self.dense.numel, pl.uniq_grad.data_ptr(), pl.n_uniq.data_ptr(), self.n_sparse(pl),
+                   self.D, ws.data_ptr(), out.data_ptr(), self.s)
+
     def enqueue_step_begin(self) -> None:
         lib().call("amid_step_begin", self.step_state.data_ptr(), self.s)
         self.step += 1

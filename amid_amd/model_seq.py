@@ -20,6 +20,8 @@ are accepted and ignored; dropout follows ``module.training``.  Two ways to trai
   reference loop   ``opt = torch.optim.Adam(model.parameters(), lr)``; ``loss.backward(); opt.step()``
                    (train_sr.py:213-215) works unchanged: backward runs the HIP kernels and hands autograd
                    the gradients (the table gradient is materialised densely for torch's optimizer);
+                   with ``amid_amd.optim.Adam`` in place of ``torch.optim.Adam`` the table gradient stays the step's
+                   unique rows and ``step()`` is the engine's one-launch dense-equivalent lazy Adam (optim.py);
   fused step       ``model.train_step(batch)`` = forward + masked BCE + backward + dense-equivalent lazy
                    Adam as one hipGraph replay -- what ``train_sr.py`` of this repo and ``bench.py`` use.
 
@@ -32,6 +34,7 @@ before the encoders, which then run over 2 * seq_len tokens (csrc/innercomp.hip)
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, Optional
 
 import torch
@@ -71,8 +74,13 @@ class _SasrecFunction(torch.autograd.Function):
         pl = eng.plan(B, T, 1 + neg.shape[1], need_grad=bool(need_grad))
         eng.stream.wait_stream(torch.cuda.current_stream())
         eng.load_batch(pl, i_node, neg, seq_d1, seq_d2)
+        loop = model._loop if model._amid_optims else None      # an amid_amd.optim.Adam drives this model (its contract: optim.py)
         if model.training:
-            eng.enqueue_step_begin()                   # fresh dropout counter per training forward
+            if loop is None or loop["fwd"] == 0:
+                eng.enqueue_step_begin()               # fresh dropout counter per training forward
+            if loop is not None:
+                loop["fwd"] += 1                       # (a second one before step() is refused there: it takes no further bump, so the
+                                                       # refusal leaves the lazy rows' stamps consistent)
         eng.enqueue_prepare(pl, sparse=need_grad)
         if need_grad and eng.table_m is not None:
             eng.enqueue_catchup(pl)                    # lazy-Adam rows must be current before they are gathered
@@ -87,6 +95,10 @@ class _SasrecFunction(torch.autograd.Function):
     def backward(ctx, *gouts):
         model, pl = ctx.model, ctx.pl
         eng: SasrecEngine = model.engine
+        loop = model._loop if model._amid_optims else None
+        if loop is not None and loop["bwd"] >= 1:
+            raise RuntimeError("amid_amd.optim.Adam: a second backward() before step() (gradient accumulation) is not supported: one plan "
+                               "holds one batch's table rows -- exactly one training-mode forward and backward between two step() calls")
         eng.stream.wait_stream(torch.cuda.current_stream())
         dsts = (pl.dp1, pl.dp2) + ((pl.dips1, pl.dips2, pl.dg1, pl.dg2) if eng.dr else ())
         with torch.cuda.stream(eng.stream):
@@ -97,10 +109,19 @@ class _SasrecFunction(torch.autograd.Function):
                     d.copy_(g.reshape(d.shape))
         eng.enqueue_backward(pl, train=ctx.train)
         grads = []
+        # every dense .grad is its view of the optimizer's flat buffer (what optim.Adam.zero_grad() installs): the engine's dense gradient is
+        # added to that buffer in ONE launch and autograd is handed nothing to accumulate -- no copy and no addition per parameter
+        if loop is not None and all(p.grad is not None and p.grad.data_ptr() == v.data_ptr() for p, v in zip(model._amid_dense_params, model._amid_gviews)):
+            with torch.cuda.stream(eng.stream):
+                model._amid_gflat.add_(eng.dense.grad)
+            torch.cuda.current_stream().wait_stream(eng.stream)
+            model._last_plan = pl
+            loop["bwd"] += 1
+            return (None,) * (6 + len(model._param_names))
         with torch.cuda.stream(eng.stream):
             for name in model._param_names:
                 if name == "item_emb_layer.emb_item.weight":
-                    if model.fused_optimizer:
+                    if model.fused_optimizer or loop is not None:
                         grads.append(None)             # rows stay in pl.uniq_ids / pl.uniq_grad for the lazy Adam
                     else:
                         U = int(pl.n_uniq.item())
@@ -111,6 +132,8 @@ class _SasrecFunction(torch.autograd.Function):
                     grads.append(eng.dense.view(name, eng.dense.grad).clone())
         torch.cuda.current_stream().wait_stream(eng.stream)
         model._last_plan = pl
+        if loop is not None:
+            loop["bwd"] += 1
         return (None, None, None, None, None, None, *grads)
 
 
@@ -161,6 +184,13 @@ class SASRec(nn.Module):
             _register_tree(self, name, nn.Parameter(eng.dense.view(name)))
         self.fused_optimizer = False            # set by train_step(): table gradient stays sparse, Adam runs in HIP
         self._last_plan = None
+        # amid_amd.optim.Adam finds the model from its parameters (a weak reference on each) and binds itself here; _loop counts the
+        # training-mode forwards and the backwards since the last step()
+        self._amid_optims: list = []
+        self._loop = {"fwd": 0, "bwd": 0}
+        me = weakref.ref(self)
+        for p in self.parameters():
+            p._amid_owner = me
 
     def _init_reference_defaults(self, seed: int) -> None:
         """Same initial distributions as the reference's modules (nn.Embedding N(0,1); nn.Linear / Conv1d /
@@ -215,6 +245,8 @@ class SASRec(nn.Module):
         (:392-398); returns the three-element tensor (loss_cls, loss_dr_e, loss_dr_r) of this batch.  Pick the Adam state with
         engine.select_optimizer() (the reference alternates two optimizers)."""
         eng = self.engine
+        if self._loop["fwd"]:
+            raise RuntimeError("train_step() between a training-mode forward and the step() of an amid_amd.optim.Adam: finish that step first")
         self.fused_optimizer = True
         B, T = seq_d1.shape
         neg = neg_samples.reshape(B, -1)

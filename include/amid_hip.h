@@ -185,6 +185,21 @@ int amid_adam_dense_f32(float* p, float* m, float* v, const float* g, long long 
 int amid_optimizer_step_f32(float* p, float* m, float* v, const float* g, long long n, float* table, float* m_tab, float* v_tab,
                             int* last, const int* uniq_ids, const int* n_uniq, int n_uniq_max, const float* uniq_grad, int D,
                             float grad_scale, const void* step_state, void* stream);
+/* ---- gradient clipping for the reference's own loop (csrc/optim_clip.hip; amid_amd/optim.py Adam.clip_grad_norm_) ----
+ * replaces: torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) over the DENSE table gradient.
+ * out[0] = sum of g^2 over g_dense[0, n_dense) and rows [0, *n_uniq) of uniq_grad [cap, D] (*n_uniq is read on the device and clamped to
+ * cap; rows at or beyond it are never read).  Two launches, a fixed order of double additions, no float atomics: a rerun gives the same
+ * bits.  n_dense = 0 (g_dense may then be null) and *n_uniq = 0 are legal.  g_dense and uniq_grad on 16-byte boundaries, ws on 8;
+ * ws: amid_grad_sqnorm_workspace_bytes() bytes, no state kept between calls. */
+long long amid_grad_sqnorm_workspace_bytes(void);
+int amid_grad_sqnorm_f32(const float* g_dense, long long n_dense, const float* uniq_grad, const int* n_uniq, int cap, int D, void* ws,
+                         float* out, void* stream);
+/* amid_optimizer_step_f32 with every gradient multiplied by grad_scale * c, c = min(1, max_norm / (sqrt(*sqnorm) + 1e-6)) (torch's clip
+ * coefficient; sqnorm is a device scalar: no host synchronisation).  max_norm = +inf leaves the bits of amid_optimizer_step_f32.
+ * n = 0 is legal here (no dense parameters). */
+int amid_optimizer_step_clip_f32(float* p, float* m, float* v, const float* g, long long n, float* table, float* m_tab, float* v_tab,
+                                 int* last, const int* uniq_ids, const int* n_uniq, int n_uniq_max, const float* uniq_grad, int D,
+                                 float grad_scale, const void* step_state, const float* sqnorm, float max_norm, void* stream);
 /* The data-parallel optimizer as ONE launch over the world's gathered chunks (the reference has no multi-GPU path: train_sr.py:473).
  * Chunk r at gathered + r * chunk_floats = [id_rows rows of D floats holding umax ascending unique int32 ids, padded with `sentinel`
  * (> every id) | umax gradient rows | at dense_off: the rank's flat dense gradient, n floats].  g <- the ranks' dense parts summed in
