@@ -16,6 +16,7 @@
 #include "tail_parts.h"
 #include "reduce_partials.h"
 #include "weights_image.h"
+#include "pool_slab.h"
 
 namespace amid {
 
@@ -140,32 +141,6 @@ __global__ __launch_bounds__(256) void lazy_adam_catchup_pos_kernel(float* __res
 //   the rest          the lazy-Adam catch-up of the compact list's rows, a wave per position (lazy_adam_catchup_pos_kernel's arithmetic)
 // Nobody waits for anybody: every role reads the batch image, which is input.  The step counter: every workgroup takes t - 1 from
 // StepState::step_done and one thread writes `step` = t, which no workgroup of this launch reads (rng.h) -- no ticket, no atomic.
-struct PoolBatch {          // a packed batch image (engine_io.py pack_epoch): [i_node B][neg B n_neg][seq_d1 B T][seq_d2 B T][domain B] ...
-    const long long* __restrict__ src;
-    int B, T, n_neg;
-    long long n_rows;
-    __device__ __forceinline__ int n_compact() const { return B * T + B * (1 + n_neg); }
-    // compact position p: sample b's own-domain sequence at p = b T + t, then the items.  Returns the id (0 when out of range, as the
-    // packing launches do -- they raise the flag) and the row of the full [2 B T + B NI] layout its gradient stands in
-    __device__ __forceinline__ int at(int p, int& row) const {
-        const int M = B * T, NI = 1 + n_neg, items0 = B + B * n_neg;
-        int word;
-        if (p < M) {
-            const int b = p / T;
-            const int dom = src[items0 + 2 * M + b] != 0 ? 1 : 0;
-            word = items0 + dom * M + p;
-            row = dom * M + p;
-        } else {
-            const int j = p - M, b = j / NI, k = j - b * NI;
-            word = k == 0 ? b : B + b * n_neg + (k - 1);
-            row = 2 * M + j;
-        }
-        const long long v = src[word];
-        return (v < 0 || v >= n_rows) ? 0 : (int)v;
-    }
-};
-struct PoolKeys { PoolBatch pb; __device__ __forceinline__ int operator()(int k) const { int row; return pb.at(k, row); } };
-
 struct StepHeadArgs {
     const long long* pool; long long stride; int n_pool; long long phase;
     long long* in_pack; int in_words;
@@ -285,6 +260,114 @@ __global__ __launch_bounds__(256) void step_head_kernel(const StepHeadArgs a, co
             replay_row(r, lj);
         }
         if (base + 64LL * n_w < n_c) __syncthreads();    // (a wave of the next round must not raise any_lag while a slow one still reads it)
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The step head on a PREPARED pool (amid_step_head_prepared_f32; pool_prepare.hip, pool_slab.h): the lists and the whole index sort of every
+// batch were made when the pool was filled, so the head builds nothing -- and the four later launches carry no sort riders.  Roles:
+//   [0, ncp)    copy: the batch image into the plan's input words, the batch's slab section by section into the plan's own buffers (every
+//               later launch reads those, untouched), n_uniq, the batch's out-of-range flag OR-ed into the plan's; one thread writes `step`
+//   the rest    the lazy-Adam catch-up over the slab's UNIQUE ids, a wave per lagging row (step_head_kernel's arithmetic): a row has one
+//               owner, so nobody claims it -- `last[r]` ends at t - 1 as there
+//   W16         the weight-image riders as the launch's last workgroups, as in step_head_kernel
+// Nobody waits for anybody: every role reads the pool and the slab, which nothing writes during an epoch.
+constexpr int PREP_SEGS = 8;
+struct PreparedHeadArgs {
+    const int* slab; long long slab_stride; SlabLayout lay;
+    // the slab's sections and where they go: segment g = n[g] ints from slab + src_off[g] to dst[g], moved as ceil(n / 4) items of 16 bytes;
+    // cum[g] = the items before segment g, behind the batch image's in_words items of 8 bytes (cum[0] = in_words)
+    int* dst[PREP_SEGS]; int src_off[PREP_SEGS]; int n[PREP_SEGS]; int cum[PREP_SEGS + 1];
+    int* n_uniq;
+    int ncp;
+};
+
+template <bool W16>
+__global__ __launch_bounds__(256) void step_head_prepared_kernel(const StepHeadArgs a, const PreparedHeadArgs q, const W16Rider wr) {
+    if constexpr (W16) {
+        const int first = (int)gridDim.x - wr.n * wr.per;
+        if ((int)blockIdx.x >= first) { w16_rider_block(wr, blockIdx.x - first); return; }
+    }
+    const long long t_pre = a.st->step_done;
+    long long which = (t_pre + a.phase) % a.n_pool;
+    if (which < 0) which += a.n_pool;
+    const int* __restrict__ sl = q.slab + which * q.slab_stride;
+    if ((int)blockIdx.x < q.ncp) {
+        const long long* __restrict__ src = a.pool + which * a.stride;
+        const int tid = blockIdx.x * 256 + threadIdx.x, nth = q.ncp * 256;
+        if (tid == 0) {
+            a.st->step = t_pre + 1;                                // (no workgroup of this launch reads `step`)
+            *q.n_uniq = sl[0];
+            if (sl[1]) atomicOr(a.err, sl[1]);
+        }
+        // ONE item per thread (the grid has a thread per item; the loop only covers a smaller grid): a load and a store, no thread walks a
+        // chain of dependent round trips
+        for (int f = tid; f < q.cum[PREP_SEGS]; f += nth) {
+            if (f < a.in_words) { a.in_pack[f] = src[f]; continue; }
+            int g = 0;
+#pragma unroll
+            for (int k = 1; k < PREP_SEGS; ++k) g += f >= q.cum[k] ? 1 : 0;
+            const int j = 4 * (f - q.cum[g]), n = q.n[g];
+            const int* __restrict__ sp = sl + q.src_off[g];
+            int* __restrict__ dp = q.dst[g];
+            if (j + 4 <= n) *(int4*)(dp + j) = *(const int4*)(sp + j);
+            else for (int k = j; k < n; ++k) dp[k] = sp[k];
+        }
+        return;
+    }
+    // ---- catch-up over the unique ids ----
+    const int bid = blockIdx.x - q.ncp, nbk = (int)gridDim.x - q.ncp - (W16 ? wr.n * wr.per : 0);
+    __shared__ IdleCoef tab[COEF_TAB];
+    StepState st = *a.st;
+    st.step = t_pre + 1;                         // (the copy's own `step` word may or may not have been written yet: not used)
+    const long long t = st.step;
+    const int lane = threadIdx.x & 63, D = a.D;
+    const int* __restrict__ uq = sl + q.lay.uniq_ids;
+    const int n_c = q.lay.n_c;
+    auto replay_row = [&](long long r, int l) {
+        for (int c = lane; c < (D >> 1); c += 64) {
+            const long long off = r * D + 2 * c;
+            const float2 p2 = *reinterpret_cast<const float2*>(a.table + off), m2 = *reinterpret_cast<const float2*>(a.m_tab + off),
+                         v2 = *reinterpret_cast<const float2*>(a.v_tab + off);
+            float p[2] = {p2.x, p2.y}, m[2] = {m2.x, m2.y}, v[2] = {v2.x, v2.y};
+            replay_elems<2>(p, m, v, (long long)l + 1, t - 1, st, tab);
+            *reinterpret_cast<float2*>(a.table + off) = make_float2(p[0], p[1]);
+            *reinterpret_cast<float2*>(a.m_tab + off) = make_float2(m[0], m[1]);
+            *reinterpret_cast<float2*>(a.v_tab + off) = make_float2(v[0], v[1]);
+        }
+    };
+    const int n_w = nbk * (blockDim.x >> 6), wv = threadIdx.x >> 6;
+    // Every id of the wave is resolved ONCE, lane j the wave's j-th (slab -> id -> stamp: two dependent loads paid side by side), and the
+    // count U is loaded beside the ids, not in front of them: an entry behind U holds an id of [0, n_rows) left by an earlier fill -- zero
+    // in a fresh slab --, so its stamp may be read; it is masked once U is here.  The coefficient table is computed by EVERY block while
+    // those loads are in flight (at the headline shape nearly every row lags: a pool of sixty batches over a table of 900 k rows), so no
+    // wave waits for a block-wide "does anybody lag" and the waves of a block run on their own.
+    auto resolve = [&](long long base, int& id, int& l) {
+        const long long i = base + wv + (long long)lane * n_w;
+        id = 0; l = 0;
+        if (i < n_c) {
+            id = uq[i];
+            if ((unsigned long long)id < (unsigned long long)a.n_rows) l = a.last[id];       // (whatever a caller's slab held before its first fill)
+        }
+    };
+    long long base = (long long)bid * (blockDim.x >> 6);
+    int id, l;
+    resolve(base, id, l);
+    const int U = sl[0];
+    fill_coef_table(tab, st);
+    while (base < U) {
+        const long long i = base + wv + (long long)lane * n_w;
+        unsigned long long todo = __ballot(i < U && l > 0 && l < t - 1);
+        while (todo != 0ull) {
+            const int j = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const long long r = __builtin_amdgcn_readlane(id, j);
+            const int lj = __builtin_amdgcn_readlane(l, j);
+            replay_row(r, lj);
+            if (lane == 0) a.last[r] = (int)(t - 1);             // (the row's only owner: no claim)
+        }
+        base += 64LL * n_w;
+        if (base < U) resolve(base, id, l);
     }
 }
 
@@ -1005,6 +1088,77 @@ extern "C" int amid_step_head_w16_f32(const long long* pool, long long pool_stri
     wr.dst = (unsigned short*)w16_dst; wr.dstT = (unsigned short*)w16t_dst; wr.planes = w_planes; wr.D = D; wr.per = (D * (D / 8) + 255) / 256;
     return step_head(pool, pool_stride, n_pool, phase, in_pack, in_words, B, T, n_neg, n_rows, idx_all, idx_c, row_c, live, err_flag, table, m, v, last,
                      D, step_state, sort_plan, stream, &wr);
+}
+
+// amid_step_head_w16_f32 on a pool prepared by amid_pool_prepare_i32 (slab / slab_stride: its slabs): the batch's slab copied into the plan's
+// buffers instead of built -- idx_all / idx_c / row_c / live as there, and pos_sorted / uniq_ids / seg_off / seg_of / n_uniq, which are taken
+// from sort_plan (required: the plan packed on (idx_c, row_c); nothing of it runs, the later launches of the step carry NO sort riders) --,
+// the catch-up over the slab's unique ids, the step counter's bump.  n_w = 0 (w_src, w16_dst NULL): no weight-image riders.
+extern "C" int amid_step_head_prepared_f32(const long long* pool, long long pool_stride, int n_pool, long long phase, long long* in_pack,
+                                           int in_words, int B, int T, int n_neg, long long n_rows, int* idx_all, int* idx_c, int* row_c,
+                                           int* live, int* err_flag, float* table, float* m, float* v, int* last, int D, void* step_state,
+                                           const void* sort_plan, const int* slab, long long slab_stride, const float* const* w_src, int n_w,
+                                           int w_planes, void* w16_dst, void* w16t_dst, void* stream) {
+    AMID_CHECK_ARG(pool && n_pool > 0 && in_pack && idx_all && idx_c && row_c && live && err_flag && table && m && v && last && step_state &&
+                   B > 0 && T > 0 && n_neg > 0 && D > 0 && (D % 4) == 0 && sort_plan && slab);
+    AMID_CHECK_ARG(in_words >= B + B * n_neg + 2 * B * T + B && 2LL * B * T + (long long)B * (1 + n_neg) <= (1LL << 28));
+    StepHeadArgs a;
+    a.pool = pool; a.stride = pool_stride; a.n_pool = n_pool; a.phase = phase; a.in_pack = in_pack; a.in_words = in_words;
+    a.B = B; a.T = T; a.n_neg = n_neg; a.n_rows = n_rows; a.idx_all = idx_all; a.idx_c = idx_c; a.row_c = row_c; a.live = live; a.err = err_flag;
+    a.table = table; a.m_tab = m; a.v_tab = v; a.last = last; a.D = D; a.st = (StepState*)step_state; a.npk = 0;
+    const SortPlan& sp = *(const SortPlan*)sort_plan;
+    PreparedHeadArgs q;
+    q.slab = slab; q.slab_stride = slab_stride; q.lay = slab_layout(B, T, n_neg);
+    if (sp.n != q.lay.n_c) return AMID_ERR_ARG;                       // the plan must be the compact list's
+    AMID_CHECK_ARG(slab_stride >= q.lay.ints && (slab_stride & 3) == 0);
+    {
+        const SlabLayout& L = q.lay;
+        int* const dst[PREP_SEGS] = {idx_all, idx_c, row_c, live, sp.pos_sorted, sp.uniq_ids, sp.seg_off, sp.seg_of};
+        const int off[PREP_SEGS] = {L.idx_all, L.idx_c, L.row_c, L.live, L.pos_sorted, L.uniq_ids, L.seg_off, L.seg_of};
+        const int n[PREP_SEGS] = {L.n_idx, L.n_c, L.n_c, B + 1, L.n_c, L.n_c, L.n_c + 1, L.n_c};
+        int cum = in_words;
+        for (int g = 0; g < PREP_SEGS; ++g) {
+            AMID_CHECK_ARG(dst[g] != nullptr && (((unsigned long long)dst[g]) & 15) == 0);
+            q.dst[g] = dst[g]; q.src_off[g] = off[g]; q.n[g] = n[g]; q.cum[g] = cum;
+            cum += (n[g] + 3) / 4;
+        }
+        q.cum[PREP_SEGS] = cum;
+    }
+    q.n_uniq = sp.n_uniq;
+    AMID_CHECK_ARG(sp.n_uniq != nullptr && (((unsigned long long)slab) & 15) == 0);
+    W16Rider wr = {};
+    if (n_w != 0) {
+        AMID_CHECK_ARG(w_src && n_w > 0 && (w_planes == 1 || w_planes == 3) && w16_dst && D == 128 && n_w * (w16t_dst ? 2 : 1) <= W16_MAX);
+        for (int i = 0; i < n_w; ++i) { AMID_CHECK_ARG(w_src[i]); wr.src[i] = w_src[i]; wr.ld[i] = (unsigned short)D; wr.tr[i] = 0; }
+        wr.n = wr.n_fwd = n_w;
+        if (w16t_dst != nullptr) {
+            for (int i = 0; i < n_w; ++i) { wr.src[n_w + i] = w_src[i]; wr.ld[n_w + i] = (unsigned short)D; wr.tr[n_w + i] = 1; }
+            wr.n = 2 * n_w;
+        }
+        wr.dst = (unsigned short*)w16_dst; wr.dstT = (unsigned short*)w16t_dst; wr.planes = w_planes; wr.D = D; wr.per = (D * (D / 8) + 255) / 256;
+    }
+    // copy workgroups: a thread per item (8 bytes of the image, 16 of a slab section)
+    int ncp = (q.cum[PREP_SEGS] + 255) / 256;
+    if (ncp > 512) ncp = 512;
+    q.ncp = ncp;
+    // catch-up: a replay is a chain of dependent steps, so a lagging row wants a wave of its own -- as many workgroups as stay resident
+    // beside the others in ONE round (8 of 256 threads per CU, as amid_step_head_f32), at most a wave per two compact positions
+    const int riders = wr.n * wr.per;
+    int resident = 2048;
+    {
+        int dev = 0, n_cu = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu > 0)
+            resident = 8 * n_cu;
+    }
+    long long blocks = ((long long)q.lay.n_c + 7) / 8;
+    const long long room = (long long)resident - ncp - riders;
+    if (room >= 256 && blocks > room) blocks = room;
+    if (blocks < 4) blocks = 4;
+    if (blocks > 16384) blocks = 16384;
+    if (riders > 0) step_head_prepared_kernel<true><<<ncp + (int)blocks + riders, 256, 0, (hipStream_t)stream>>>(a, q, wr);
+    else step_head_prepared_kernel<false><<<ncp + (int)blocks, 256, 0, (hipStream_t)stream>>>(a, q, wr);
+    AMID_LAUNCH_CHECK();
+    return AMID_OK;
 }
 
 // amid_optimizer_step_f32 for a step whose gradient tail ran phase A of the segment reduce only (amid_grad_tail_live_f32): the runs of

@@ -858,8 +858,9 @@ static int sas_wgrad(const float* const* dy, const float* const* x, int n_layers
     AMID_CHECK_ARG(dy && x && w_part && b_part && (n_layers == 1 || n_layers == 2) && M > 0 && splits > 0);
     AMID_CHECK_ARG(!row_domain || (B > 0 && T > 0 && (long long)B * T == M));
     WgradArgs a = {};
-    if (ln_stat != nullptr) {          // (the six-pair build with the rider: checked below)
-        AMID_CHECK_ARG(ln1_w && ln1_b && ln2_w && ln2_b && sort_plan != nullptr);
+    if (ln_stat != nullptr) {          // (the builds on bf16 pieces: with the rider checked below, without it the six-pair build at D 128)
+        AMID_CHECK_ARG(ln1_w && ln1_b && ln2_w && ln2_b);
+        if (sort_plan == nullptr && !(mma_bf16 == 3 && D == 128)) return AMID_ERR_UNSUPPORTED;
         for (int l = 0; l < n_layers; ++l) {
             AMID_CHECK_ARG(ln_stat[l] != nullptr);
             a.ln_stat[l] = ln_stat[l];
@@ -952,6 +953,16 @@ extern "C" int amid_sas_wgrad_rows_sort_ln_f32(const float* const* dy, const flo
                                                const float* const* ln1_b, const float* const* ln2_w, const float* const* ln2_b, void* stream) {
     AMID_CHECK_ARG(sort_plan != nullptr && row_domain != nullptr && ln_stat != nullptr);
     return sas_wgrad(dy, x, n_layers, M, D, splits, w_part, b_part, row_domain, B, T, mma_bf16, stream, sort_plan, ln_stat, ln1_w, ln1_b, ln2_w, ln2_b);
+}
+
+// amid_sas_wgrad_rows_sort_ln_f32 WITHOUT the rider's z-slice: the weight gradients of a step whose index sort was done when its input pool
+// was filled (amid_pool_prepare_i32).  mma_bf16 = 3, D = 128.
+extern "C" int amid_sas_wgrad_rows_ln_f32(const float* const* dy, const float* const* x, int n_layers, int M, int D, int splits,
+                                          float* const* w_part, float* const* b_part, const long long* row_domain, int B, int T,
+                                          int mma_bf16, const float* const* ln_stat, const float* const* ln1_w, const float* const* ln1_b,
+                                          const float* const* ln2_w, const float* const* ln2_b, void* stream) {
+    AMID_CHECK_ARG(row_domain != nullptr && ln_stat != nullptr);
+    return sas_wgrad(dy, x, n_layers, M, D, splits, w_part, b_part, row_domain, B, T, mma_bf16, stream, nullptr, ln_stat, ln1_w, ln1_b, ln2_w, ln2_b);
 }
 
 extern "C" int amid_transpose_weights_f32(const float* const* src, float* const* dst, int n, int D, void* stream) {

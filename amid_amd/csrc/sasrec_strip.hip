@@ -399,7 +399,8 @@ __global__ __launch_bounds__(STRIP_THREADS) void strip_ffn_bwd_kernel(const Stri
 }
 
 // FFN = true: the layer below's feed-forward / out-projection backward continues on d x in registers (d x is then never stored)
-// RIDER: as strip_ffn_bwd_kernel (with FFN: phase 3, pass 1's counts; without: phase 4, the scatter of pass 1)
+// RIDER: as strip_ffn_bwd_kernel (with FFN: phase 3, pass 1's counts; without: phase 4, the scatter of pass 1); -1 (with FFN): the scorer sums'
+// workgroups WITHOUT a sort rider (a step on a prepared pool: the sort was done when the pool was filled, pool_prepare.hip)
 template <int D, bool FFN, int RIDER, int BF = 0>
 __global__ __launch_bounds__(STRIP_THREADS) void strip_qkv_bwd_kernel(const StripQkvBwdArgs a, const StripFfnBwdArgs f, const ScorerSum ss,
                                                                       const StripGeom sg, const SortRider rd) {
@@ -417,7 +418,7 @@ __global__ __launch_bounds__(STRIP_THREADS) void strip_qkv_bwd_kernel(const Stri
             if (bid >= first) { scorer_sum_block(ss, bid - first, (scorer_lds_f4*)smem); return; }
         }
     }
-    if constexpr (RIDER != 0) {
+    if constexpr (RIDER > 0) {
         if (bid < rd.plan.nblk) { sort_phase_ct<RIDER>(rd.plan, bid, smem); return; }
         bid -= rd.plan.nblk;
     }
@@ -777,6 +778,8 @@ struct StripQkvBwdCall {
 // (the rider's phase: 3 with the fused feed-forward backward, 4 without; the scorer sums' workgroups -- ss.nblk, 0 without them -- behind the sort's)
 template <int D, bool FFN, int BF>
 static int launch_qkv_bwd(const StripGeom& sg, const SortRider& rd, void* stream, const StripQkvBwdArgs& a, const StripFfnBwdArgs& f, const ScorerSum& ss) {
+    if constexpr (FFN && D == 128 && (BF == 3 || BF == 1))
+        if (!rd.phase && ss.nblk > 0) return launch_strip_rider<strip_qkv_bwd_kernel<D, FFN, -1, BF>, D>(sg, rd, ss.nblk, stream, a, f, ss);
     return rd.phase ? launch_strip_rider<strip_qkv_bwd_kernel<D, FFN, FFN ? 3 : 4, BF>, D>(sg, rd, ss.nblk, stream, a, f, ss)
                     : launch_strip_rider<strip_qkv_bwd_kernel<D, FFN, 0, BF>, D>(sg, rd, 0, stream, a, f, ss);
 }
@@ -805,7 +808,7 @@ static int strip_qkv_bwd(const StripQkvBwdCall& c, const StripBwdLaunch& l) {
     if (rd.phase != 0 && rd.phase != (ffn ? 3 : 4)) return AMID_ERR_UNSUPPORTED;      // phase 3 with the fused feed-forward backward, 4 without
     ScorerSum ss = {};
     if (c.scorer != nullptr) {
-        if (!(rd.phase != 0 && ffn && D == 128 && (mma_bf16 == 3 || mma_bf16 == 1))) return AMID_ERR_UNSUPPORTED;       // the riders' host: the middle launch on bf16 pieces / one piece
+        if (!(ffn && D == 128 && (mma_bf16 == 3 || mma_bf16 == 1))) return AMID_ERR_UNSUPPORTED;       // the riders' host: the middle launch on bf16 pieces / one piece (with or without a sort rider)
         ss = *c.scorer;
     }
     void* const st = l.stream;
@@ -859,6 +862,24 @@ extern "C" int amid_sas_strip_qkv_bwd_sort_scorer_f32(const float* dq, const flo
     AMID_CHECK_ARG(((((unsigned long long)dW1) | ((unsigned long long)u) | ((unsigned long long)items)) & 15) == 0);
     const ScorerSum ss = scorer_sum_args(hidg, u, items, B, NI, D, hid, dW1, db1, dW2, db2);
     STRIP_QKV_BWD_CALL(c); STRIP_QKV_BWD_FFN(c); c.scorer = &ss; STRIP_BWD_LAUNCH(l); STRIP_BWD_RIDER(l);
+    return strip_qkv_bwd(c, l);
+}
+
+// amid_sas_strip_qkv_bwd_sort_scorer_f32 WITHOUT the sort rider: the middle launch of a step whose index sort was done when its input pool was
+// filled (amid_pool_prepare_i32) -- the tiles and the scorer sums' workgroups only.  D = 128, mma_bf16 = 3 or 1.
+extern "C" int amid_sas_strip_qkv_bwd_scorer_f32(const float* dq, const float* dk, const float* dv, const float* dr, const float* x,
+                                                 const float* const* ln_w, const float* const* wqT, const float* const* wkT,
+                                                 const float* const* wvT, float ln_eps, int B, int T, int D, const int* live,
+                                                 float* ln_part, const unsigned char* tmq, const float* fh, const float* fr,
+                                                 const float* const* fln_w, const float* const* fw1T, const float* const* fw2T,
+                                                 const float* const* fwoT, int flayer, const void* step_state, int train, float p_drop,
+                                                 float* fdpre2, float* fdpre1, float* fdr, float* fd_o, float* fln_part, int mma_bf16,
+                                                 const float* hidg, const float* u, const float* items, int NI, int hid, float* dW1, float* db1,
+                                                 float* dW2, float* db2, void* stream) {
+    AMID_CHECK_ARG(fh != nullptr && hidg && u && items && NI > 0 && hid > 0 && dW1 && db1 && dW2 && db2);
+    AMID_CHECK_ARG(((((unsigned long long)dW1) | ((unsigned long long)u) | ((unsigned long long)items)) & 15) == 0);
+    const ScorerSum ss = scorer_sum_args(hidg, u, items, B, NI, D, hid, dW1, db1, dW2, db2);
+    STRIP_QKV_BWD_CALL(c); STRIP_QKV_BWD_FFN(c); c.scorer = &ss; STRIP_BWD_LAUNCH(l);
     return strip_qkv_bwd(c, l);
 }
 

@@ -339,6 +339,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         # index list are one launch; the later phases ride in the backward strips and the weight gradients; no embedding-backward launch
         pl.tail2 = bool(ent is not None and bump_step and sparse and defer_sort and with_live and self._tail2_ok(pl))
         pl.gather_on_fwd = False
+        pl.prepared = False
         if pl.tail2:
             pool, phase = ent
             self._ensure_opt_state()
@@ -349,13 +350,23 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             # the step's gather as the prologue of its forward (amid_sas_seq_fwd_gather_*_f32): K1's riders -- the weight images of the forward
             # and of the backward strips -- move to this launch's last workgroups
             pl.gather_on_fwd = bool(self.GATHER_ON_FWD and self._fwd_on_pieces(pl, shp.B, shp.Tenc) and self._p3_bwd_for(pl) and shp.T == shp.Tenc)
-            if pl.gather_on_fwd:
+            # a pool prepared at pool fill (PREPARED_POOL, engine_io.py): the head copies the batch's slab -- lists, sort, runs -- into the plan's
+            # buffers instead of building it, and the four later launches that hosted the sort's phases 2 .. 5 run without riders
+            slabs = self.pool_slabs(pl)
+            pl.prepared = bool(self.PREPARED_POOL and slabs is not None and getattr(self, "_in_train_step", False) and self.compute != "bf16")
+            if pl.prepared:
+                w = (None, 0, 0, None, None)
+                if pl.gather_on_fwd:
+                    src, w16 = self._w16_images(3)
+                    w = (src, 24, 3, w16.data_ptr(), self._wT16x3_buf().data_ptr())
+                L.call("amid_step_head_prepared_f32", *head, slabs[0].data_ptr(), slabs[0].stride(0), *w, s)
+            elif pl.gather_on_fwd:
                 src, w16 = self._w16_images(3)
                 L.call("amid_step_head_w16_f32", *head, src, 24, 3, w16.data_ptr(), self._wT16x3_buf().data_ptr(), s)
             else:
                 L.call("amid_step_head_f32", *head, s)
             self.step += 1
-            pl.compact, pl.riding, pl.chain = True, True, False
+            pl.compact, pl.riding, pl.chain = True, not pl.prepared, False
             self._sort_owed = False
             return
         if ent is not None:
@@ -517,6 +528,12 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
     GATHER_ON_FWD = True         # ... and its gather K1 as the prologue of the forward's workgroups: nine (the weight images by the step head's riders)
     FUSED_SPANS = True           # every single-GPU train step: the segment reduce's second phase inside the optimizer launch (round 5)
     FUSED_TAIL = True
+    # The folded single-GPU step on a pool PREPARED at pool fill (csrc/pool_prepare.hip; set_input_pool / refill_input_pool make one slab per
+    # batch: index lists, live list, the stable sort of the compact list and its runs -- all functions of the batch alone): the step head
+    # copies its batch's slab instead of building it (amid_step_head_prepared_f32) and the sort's phases 2 .. 5 leave the strips and the
+    # weight-gradient launch.  Tables of up to 2^20 rows; data parallel, bf16 and the other models keep the per-step path.  False: the
+    # step is bit for bit the per-step one (tests/test_gpu_prepared_pool.py; `bench.py --set PREPARED_POOL=0`).
+    PREPARED_POOL = True
 
     def _coll(self, fn) -> None:
         """A collective in the MIDDLE of a step (InterComp's / InnerComp's gathers and reductions under data parallel).  Eagerly: run it.
@@ -1128,13 +1145,15 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             attn_bwd(1)
             # layer 1's q / k / v + LayerNorm1 backward and layer 0's feed-forward / out-projection backward: one launch
             if t2:      # ... whose idle CUs also sum the scorer's weight gradients from the head's per-sample hidden gradients
-                L.call_named("amid_sas_strip_qkv_bwd_sort_scorer_f32", self._scorer(("dW1", "db1", "dW2", "db2"), grad=True),
+                # (a prepared pool: the same launch without the sort's workgroups)
+                mid = ("amid_sas_strip_qkv_bwd_sort_scorer_f32", dict(sort_plan=plan_addr, sort_phase=3)) if riding else ("amid_sas_strip_qkv_bwd_scorer_f32", {})
+                L.call_named(mid[0], self._scorer(("dW1", "db1", "dW2", "db2"), grad=True), **mid[1],
                              dq=pl.dq_l[1].data_ptr(), dk=pl.dk_l[1].data_ptr(), dv=pl.dv_l[1].data_ptr(), dr=pl.dr[1].data_ptr(),
                              x=pl.x[1].data_ptr(), ln_w=self._pp("sac{d}.attention_layernorms.1.weight"), wqT=self._wT(1, 0), wkT=self._wT(1, 1),
                              wvT=self._wT(1, 2), ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, live=lv, ln_part=ln1p[1].data_ptr(), tmq=tm, fh=h0, fr=r0,
                              fln_w=lnw0, fw1T=w1T0, fw2T=w2T0, fwoT=woT0, flayer=0, step_state=st, train=tr, p_drop=SASREC_P_DROP,
                              fdpre2=pl.dpre2[0].data_ptr(), fdpre1=pl.dpre1[0].data_ptr(), fdr=pl.dr[0].data_ptr(), fd_o=pl.d_o.data_ptr(),
-                             fln_part=ln2p[0].data_ptr(), sort_plan=plan_addr, sort_phase=3, mma_bf16=bf, hidg=self._hidg(pl).data_ptr(),
+                             fln_part=ln2p[0].data_ptr(), mma_bf16=bf, hidg=self._hidg(pl).data_ptr(),
                              u=pl.u.data_ptr(), items=items, NI=NI, hid=self.hid, stream=s)
             else:
                 L.call(f"amid_sas_strip_qkv_bwd{sfx}_f32", pl.dq_l[1].data_ptr(), pl.dk_l[1].data_ptr(), pl.dv_l[1].data_ptr(), pl.dr[1].data_ptr(),
@@ -1145,7 +1164,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             if t2:      # ... with the embedding layer's backward applied on the strip (no amid_embed_bwd launch)
                 L.call("amid_sas_strip_qkv_bwd_emb_f32", pl.dq_l[0].data_ptr(), pl.dk_l[0].data_ptr(), pl.dv_l[0].data_ptr(), pl.dr[0].data_ptr(),
                        pl.x[0].data_ptr(), self._pp("sac{d}.attention_layernorms.0.weight"), self._wT(0, 0), self._wT(0, 1), self._wT(0, 2),
-                       SASREC_LN_EPS, B, T, D, lv, dx_in, ln1p[0].data_ptr(), pl.tmq.data_ptr(), st, tr, SASREC_P_DROP, plan_addr, 4, bf, s)
+                       SASREC_LN_EPS, B, T, D, lv, dx_in, ln1p[0].data_ptr(), pl.tmq.data_ptr(), st, tr, SASREC_P_DROP, plan_addr, 4 if riding else 0, bf, s)
             else:
                 L.call(f"amid_sas_strip_qkv_bwd{sfx}_f32", pl.dq_l[0].data_ptr(), pl.dk_l[0].data_ptr(), pl.dv_l[0].data_ptr(), pl.dr[0].data_ptr(),
                        pl.x[0].data_ptr(), self._pp("sac{d}.attention_layernorms.0.weight"), self._wT(0, 0), self._wT(0, 1), self._wT(0, 2),
@@ -1185,11 +1204,16 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
                     wmode = self._wgrad_mode(D)
                 finally:
                     self._wgrad_one = False
-                # (of the families it takes the four LayerNorm ones)
-                L.call_named("amid_sas_wgrad_rows_sort_ln_f32", self._fams(), dy=ptr_array(dy), x=ptr_array(xx), n_layers=2, M=M, D=D,
+                # (of the families it takes the four LayerNorm ones; a prepared pool: no rider z-slice)
+                wg = ("amid_sas_wgrad_rows_sort_ln_f32", dict(sort_plan=self._sort_plan_c(pl))) if pl.riding else ("amid_sas_wgrad_rows_ln_f32", {})
+                L.call_named(wg[0], self._fams(), dy=ptr_array(dy), x=ptr_array(xx), n_layers=2, M=M, D=D,
                              splits=pl.splits, w_part=ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]),
                              b_part=ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]), row_domain=self._own_rows(pl), B=B, T=T,
-                             mma_bf16=wmode, sort_plan=self._sort_plan_c(pl), ln_stat=self._ln_stat(pl)[1], stream=s)
+                             mma_bf16=wmode, ln_stat=self._ln_stat(pl)[1], stream=s, **wg[1])
+            elif not pl.riding:
+                L.call("amid_sas_wgrad_rows_f32", ptr_array(dy), ptr_array(xx), 2, M, D, pl.splits,
+                       ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]), ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]),
+                       self._own_rows(pl), B, T, self._wgrad_mode(D), s)
             else:
                 L.call("amid_sas_wgrad_rows_sort_f32", ptr_array(dy), ptr_array(xx), 2, M, D, pl.splits,
                        ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]), ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]),

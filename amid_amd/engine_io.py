@@ -67,8 +67,10 @@ class InputMixin:
                     or pool.device != pl.in_pack.device:
                 raise ValueError(f"input pool must be a device int64 [n, {pl.in_words}] tensor with contiguous rows")
             pl.pools[key] = [pool, (-self.step) % pool.shape[0]]
+            self._prepare_pool(pl, key, pool, alloc=True)
         else:
             pl.pools.pop(key, None)
+            getattr(pl, "slabs", {}).pop(key, None)
         torch.cuda.synchronize(self.device)
         if getattr(pl, "graphs", None):               # the pool pointer is baked into captured launches
             pl.graphs.pop(key, None)
@@ -92,7 +94,50 @@ class InputMixin:
             return False
         with torch.cuda.stream(self.stream):
             ent[0].copy_(pool, non_blocking=True)
+        self._prepare_pool(pl, self._graph_key(), ent[0], alloc=False)      # (in place, behind the copy on the engine's stream: the graphs keep their addresses)
         return True
+
+    def _prepared_pool_ok(self, pl: SasrecPlan, n_pool: int) -> bool:
+        """Whether this engine's train steps on `pl` can take a pool prepared at pool fill: the switch, the single-GPU folded fp32 step
+        (decided per step in enqueue_prepare; here its shape conditions), keys within the prepare's 1 024-bin sort."""
+        if not getattr(self, "PREPARED_POOL", False) or not hasattr(self, "_tail2_ok") or getattr(self, "compute", "") == "bf16":
+            return False
+        shp = pl.shape
+        if lib().value("amid_pool_prepare_workspace_bytes", n_pool, shp.B, shp.T, shp.NI - 1, self.n_rows) <= 0:
+            return False
+        saved = getattr(self, "_in_train_step", False)
+        self._in_train_step = True
+        try:
+            return bool(self._tail2_ok(pl))
+        finally:
+            self._in_train_step = saved
+
+    def _prepare_pool(self, pl: SasrecPlan, key, pool: torch.Tensor, alloc: bool) -> None:
+        """One slab per batch of `pool` (csrc/pool_slab.h) by amid_pool_prepare_i32 on the engine's stream.  alloc: (re)allocate slabs and
+        workspace for this pool -- or drop them when the prepared path does not apply; otherwise re-prepare the existing ones in place."""
+        if not hasattr(pl, "slabs"):
+            pl.slabs = {}                             # (Adam state, objective) -> (slabs [n_pool, slab_ints] int32, workspace)
+        L, shp, n_pool = lib(), pl.shape, pool.shape[0]
+        if alloc:
+            pl.slabs.pop(key, None)
+            if not self._prepared_pool_ok(pl, n_pool):
+                return
+            ints = L.value("amid_pool_slab_ints", shp.B, shp.T, shp.NI - 1)
+            slab = torch.zeros(n_pool, ints, dtype=torch.int32, device=pool.device)
+            ws = torch.empty(L.value("amid_pool_prepare_workspace_bytes", n_pool, shp.B, shp.T, shp.NI - 1, self.n_rows), dtype=torch.uint8,
+                             device=pool.device)
+            pl.slabs[key] = (slab, ws)
+            torch.cuda.synchronize(self.device)      # (allocated and zero-filled on torch's stream, the pool maybe written there too)
+        ent = pl.slabs.get(key)
+        if ent is None:
+            return
+        slab, ws = ent
+        L.call("amid_pool_prepare_i32", pool.data_ptr(), pool.stride(0), n_pool, pl.in_words, shp.B, shp.T, shp.NI - 1, self.n_rows,
+               slab.data_ptr(), slab.stride(0), ws.data_ptr(), self.s)
+
+    def pool_slabs(self, pl: SasrecPlan):
+        """(slabs, workspace) of the pool installed for the current (Adam state, objective), or None when it was not prepared."""
+        return pl.slabs.get(self._graph_key()) if getattr(pl, "slabs", None) else None
 
     def load_packed(self, pl: SasrecPlan, packed: torch.Tensor) -> None:
         if self.input_pool(pl) is not None:

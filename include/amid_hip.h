@@ -1228,6 +1228,43 @@ int amid_gru_rec_bwd_f32(const float* dh, const float* gates, const float* ghn, 
 int amid_gru_dx_f32(const float* dgi, const float* const* w_ih, int B, int T, int D, const int* live, int zero_dead, float* dx,
                     void* stream);
 
+/* ---- an input pool PREPARED at pool fill -----------------------------------------------------
+ * What amid_step_head_f32's packing role and the five phases of the step's index sort compute is a function of the batch alone, and the
+ * pool (SasrecEngine.set_input_pool) holds an epoch's batches: amid_pool_prepare_i32 computes it for every batch of the pool in five
+ * launches (batch index in the grid) into one slab per batch -- amid_pool_slab_ints(B, T, n_neg) int32 words:
+ *   hdr [16] ([0] n_uniq, [1] the batch's out-of-range flag) | idx_all [2 B T + B NI] | idx_c | row_c [n_c = B T + B NI] | live [B + 1] |
+ *   pos_sorted [n_c] | uniq_ids [n_c] | seg_off [n_c + 1] | seg_of [n_c], every section on a 16-byte border
+ * with the sort of amid_sort_unique_rows_i32(idx_c, row_c) (the same stable two-pass radix sort, the same permutation).  Keys below 2^20
+ * (n_rows <= 2^20); AMID_ERR_UNSUPPORTED beyond, and amid_pool_prepare_workspace_bytes is then 0.  slab_stride: ints between two batches'
+ * slabs (>= amid_pool_slab_ints, a multiple of 4); slab and workspace 16-byte aligned; the workspace is cleared by the call.
+ * amid_step_head_prepared_f32: amid_step_head_w16_f32 on such a pool -- the batch's slab is copied into idx_all / idx_c / row_c / live and
+ * into the pos_sorted / uniq_ids / seg_off / seg_of / n_uniq of sort_plan (required; packed on (idx_c, row_c); none of its phases runs, and
+ * the step's later launches carry no sort riders), the batch's flag is OR-ed into err_flag, the catch-up walks the slab's unique ids.
+ * n_w = 0: no weight-image riders.
+ * amid_sas_strip_qkv_bwd_scorer_f32 / amid_sas_wgrad_rows_ln_f32: amid_sas_strip_qkv_bwd_sort_scorer_f32 / amid_sas_wgrad_rows_sort_ln_f32
+ * without the sort rider (D = 128; mma_bf16 = 3 or 1 / 3). */
+long long amid_pool_slab_ints(int B, int T, int n_neg);
+long long amid_pool_prepare_workspace_bytes(int n_pool, int B, int T, int n_neg, long long n_rows);
+int amid_pool_prepare_i32(const long long* pool, long long pool_stride, int n_pool, int in_words, int B, int T, int n_neg, long long n_rows,
+                          int* slab, long long slab_stride, void* workspace, void* stream);
+int amid_step_head_prepared_f32(const long long* pool, long long pool_stride, int n_pool, long long phase, long long* in_pack, int in_words,
+                                int B, int T, int n_neg, long long n_rows, int* idx_all, int* idx_c, int* row_c, int* live, int* err_flag,
+                                float* table, float* m, float* v, int* last, int D, void* step_state, const void* sort_plan, const int* slab,
+                                long long slab_stride, const float* const* w_src, int n_w, int w_planes, void* w16_dst, void* w16t_dst,
+                                void* stream);
+int amid_sas_strip_qkv_bwd_scorer_f32(const float* dq, const float* dk, const float* dv, const float* dr, const float* x,
+                                      const float* const* ln_w, const float* const* wqT, const float* const* wkT, const float* const* wvT,
+                                      float ln_eps, int B, int T, int D, const int* live, float* ln_part, const unsigned char* tmq,
+                                      const float* fh, const float* fr, const float* const* fln_w, const float* const* fw1T,
+                                      const float* const* fw2T, const float* const* fwoT, int flayer, const void* step_state, int train,
+                                      float p_drop, float* fdpre2, float* fdpre1, float* fdr, float* fd_o, float* fln_part, int mma_bf16,
+                                      const float* hidg, const float* u, const float* items, int NI, int hid, float* dW1, float* db1,
+                                      float* dW2, float* db2, void* stream);
+int amid_sas_wgrad_rows_ln_f32(const float* const* dy, const float* const* x, int n_layers, int M, int D, int splits, float* const* w_part,
+                               float* const* b_part, const long long* row_domain, int B, int T, int mma_bf16, const float* const* ln_stat,
+                               const float* const* ln1_w, const float* const* ln1_b, const float* const* ln2_w, const float* const* ln2_b,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
