@@ -28,31 +28,15 @@ __global__ __launch_bounds__(256) void lazy_adam_rows_kernel(float* __restrict__
                                                              const StepState* __restrict__ stp, float grad_scale) {
     __shared__ IdleCoef tab[COEF_TAB];
     const StepState st = *stp;
-    const long long t = st.step;
     const int U = *n_uniq_p;
     const int sub = threadIdx.x & 31;
-    const int q = D >> 2;
     const int hw0 = blockIdx.x * (blockDim.x >> 5) + (threadIdx.x >> 5), n_hw = gridDim.x * (blockDim.x >> 5);
     if (blockIdx.x * (blockDim.x >> 5) >= U) return;              // block-uniform: nothing to do for this block
     fill_coef_table(tab, st);
     const AdamCoef cnow = adam_coef_now(st);
     for (int u = hw0; u < U; u += n_hw) {
-        const long long r = uniq_ids[u];
-        const long long l = last[r];
-        const bool lag = (l > 0 && l < t - 1);
-        if (MODE == 0 && !lag) continue;
-        for (int c = sub; c < q; c += 32) {
-            const long long off = r * D + 4 * c;
-            float4 p = ld4(table + off), m = ld4(m_tab + off), v = ld4(v_tab + off);
-            if (lag) replay_quad(p, m, v, l + 1, t - 1, st, tab);
-            if (MODE == 1) {
-                const float4 g = f4scale(ld4(uniq_grad + (long long)u * D + 4 * c), grad_scale);
-                adam_quad(p, m, v, g, cnow);
-            }
-            st4(table + off, p); st4(m_tab + off, m); st4(v_tab + off, v);
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (sub == 0) last[r] = (MODE == 1) ? (int)t : (int)(t - 1);
+        const auto grad = [&](int c) { return ld4(uniq_grad + (long long)u * D + 4 * c); };
+        halfwave_row<MODE == 1 ? ROW_STEP : ROW_CATCHUP>(table, m_tab, v_tab, last, uniq_ids[u], D, sub, st, tab, cnow, grad_scale, grad);
     }
 }
 
@@ -79,27 +63,10 @@ __global__ __launch_bounds__(256) void lazy_adam_catchup_pos_kernel(float* __res
     const StepState st = *stp;
     const long long t = st.step;
     const int lane = threadIdx.x & 63;
-    // replay row r from its stamp l (claimed by this wave): two elements per lane -- a replay is a chain of dependent steps bound by the
-    // quarter-rate sqrt / rcp, the fewer elements a lane carries the shorter the chain
-    auto replay_row = [&](long long r, int l) {
-        for (int c = lane; c < (D >> 1); c += 64) {
-            const long long off = r * D + 2 * c;
-            // (non-temporal: a lagging row is read once per step and the tables are far larger than the caches -- the stress's launch 140.5 -> 136.7 us)
-            typedef float nt_f2 __attribute__((ext_vector_type(2)));
-            const nt_f2 pn = __builtin_nontemporal_load((const nt_f2*)(table + off)), mn = __builtin_nontemporal_load((const nt_f2*)(m_tab + off)),
-                        vn = __builtin_nontemporal_load((const nt_f2*)(v_tab + off));
-            const float2 p2 = make_float2(pn[0], pn[1]), m2 = make_float2(mn[0], mn[1]), v2 = make_float2(vn[0], vn[1]);
-            float p[2] = {p2.x, p2.y}, m[2] = {m2.x, m2.y}, v[2] = {v2.x, v2.y};
-            replay_elems<2>(p, m, v, (long long)l + 1, t - 1, st, tab);
-            *reinterpret_cast<float2*>(table + off) = make_float2(p[0], p[1]);
-            *reinterpret_cast<float2*>(m_tab + off) = make_float2(m[0], m[1]);
-            *reinterpret_cast<float2*>(v_tab + off) = make_float2(v[0], v[1]);
-        }
-    };
-    // a WAVE per lagging row (a replay is a chain of dependent steps bound by the quarter-rate sqrt / rcp: the fewer elements a lane carries,
-    // the shorter the chain), but the wave's positions are RESOLVED side by side first -- lane j the wave's j-th: index -> stamp is a chain
-    // of two dependent loads, paid once per 64 positions instead of once per position (round 5, as step_head_kernel: at the cfg 5 stress
-    // every wave walks six to seven positions and the launch was a chain of round trips, 168 us for 650 MB)
+    // a WAVE per lagging row (wave_replay_row, non-temporal: this launch reads a lagging row once), but the wave's positions are RESOLVED
+    // side by side first -- lane j the wave's j-th: index -> stamp is a chain of two dependent loads, paid once per 64 positions instead of
+    // once per position (round 5: at the cfg 5 stress every wave walks six to seven positions and the launch was a chain of round trips,
+    // 168 us for 650 MB)
     const int n_w = nbk * (blockDim.x >> 6), wv = threadIdx.x >> 6;
     if (threadIdx.x == 0) any_lag = 0;
     __syncthreads();
@@ -108,7 +75,7 @@ __global__ __launch_bounds__(256) void lazy_adam_catchup_pos_kernel(float* __res
         const long long i = base + wv + (long long)lane * n_w;
         int id = 0, l = 0;
         if (i < n_idx) { id = idx[i]; l = last[id]; }
-        const bool lag = l > 0 && l < t - 1;
+        const bool lag = row_owes(l, catchup_end(t));
         const unsigned long long lagging = __ballot(lag);
         if (lagging != 0ull && lane == 0) any_lag = 1;
         __syncthreads();
@@ -120,10 +87,10 @@ __global__ __launch_bounds__(256) void lazy_adam_catchup_pos_kernel(float* __res
             const long long r = __builtin_amdgcn_readlane(id, j);
             const int lj = __builtin_amdgcn_readlane(l, j);
             int won = 0;
-            if (lane == 0) won = (atomicCAS(&last[r], lj, (int)(t - 1)) == lj) ? 1 : 0;     // claim the row for this wave
+            if (lane == 0) won = (atomicCAS(&last[r], lj, (int)catchup_end(t)) == lj) ? 1 : 0;     // claim the row for this wave
             won = __builtin_amdgcn_readfirstlane(won);
             if (!won) continue;
-            replay_row(r, lj);
+            wave_replay_row<true>(table, m_tab, v_tab, r, lj, D, lane, st, tab);
         }
         if (base + 64LL * n_w < n_idx) __syncthreads();    // (a wave of the next round must not raise any_lag while a slow one still reads it)
     }
@@ -138,7 +105,7 @@ __global__ __launch_bounds__(256) void lazy_adam_catchup_pos_kernel(float* __res
 //   [nrb, nrb + npk)  the packing: the image mirrored into the plan's static input words, the full index list (the gather K1 and the head
 //                     read it), the compact list (ids + rows of the full layout: what the sort's later phases, the segment reduce and the
 //                     row Adam run on), the live-sequence list (last packing workgroup)
-//   the rest          the lazy-Adam catch-up of the compact list's rows, a wave per position (lazy_adam_catchup_pos_kernel's arithmetic)
+//   the rest          the lazy-Adam catch-up of the compact list's rows, a wave per position (adam_replay.h wave_replay_row)
 // Nobody waits for anybody: every role reads the batch image, which is input.  The step counter: every workgroup takes t - 1 from
 // StepState::step_done and one thread writes `step` = t, which no workgroup of this launch reads (rng.h) -- no ticket, no atomic.
 struct StepHeadArgs {
@@ -201,7 +168,7 @@ __global__ __launch_bounds__(256) void step_head_kernel(const StepHeadArgs a, co
         }
         return;
     }
-    // ---- catch-up over the compact positions (lazy_adam_catchup_pos_kernel with the ids read from the image) ----
+    // ---- catch-up over the compact positions, the ids read from the image ----
 #ifdef AMID_EXP_HEAD_NO_CATCHUP     // (variant libraries only, profiles/tools/build_variant.sh: what the launch costs without this role -- 13.1 of 16.6 us)
     return;
 #endif
@@ -211,19 +178,7 @@ __global__ __launch_bounds__(256) void step_head_kernel(const StepHeadArgs a, co
     StepState st = *a.st;
     st.step = t_pre + 1;                         // (the copy's own `step` word may or may not have been written yet: not used)
     const long long t = st.step;
-    const int lane = threadIdx.x & 63, D = a.D;
-    auto replay_row = [&](long long r, int l) {
-        for (int c = lane; c < (D >> 1); c += 64) {
-            const long long off = r * D + 2 * c;
-            const float2 p2 = *reinterpret_cast<const float2*>(a.table + off), m2 = *reinterpret_cast<const float2*>(a.m_tab + off),
-                         v2 = *reinterpret_cast<const float2*>(a.v_tab + off);
-            float p[2] = {p2.x, p2.y}, m[2] = {m2.x, m2.y}, v[2] = {v2.x, v2.y};
-            replay_elems<2>(p, m, v, (long long)l + 1, t - 1, st, tab);
-            *reinterpret_cast<float2*>(a.table + off) = make_float2(p[0], p[1]);
-            *reinterpret_cast<float2*>(a.m_tab + off) = make_float2(m[0], m[1]);
-            *reinterpret_cast<float2*>(a.v_tab + off) = make_float2(v[0], v[1]);
-        }
-    };
+    const int lane = threadIdx.x & 63;
     const int n_w = nbk * (blockDim.x >> 6);
     if (threadIdx.x == 0) any_lag = 0;
     __syncthreads();
@@ -241,7 +196,7 @@ __global__ __launch_bounds__(256) void step_head_kernel(const StepHeadArgs a, co
             id = pb.at((int)i, row);
             l = a.last[id];
         }
-        const bool lag = l > 0 && l < t - 1;
+        const bool lag = row_owes(l, catchup_end(t));
         const unsigned long long lagging = __ballot(lag);
         if (lagging != 0ull && lane == 0) any_lag = 1;
         // (the table is needed by the waves that replay; a block whose waves all find nothing skips it)
@@ -254,10 +209,10 @@ __global__ __launch_bounds__(256) void step_head_kernel(const StepHeadArgs a, co
             const long long r = __builtin_amdgcn_readlane(id, j);
             const int lj = __builtin_amdgcn_readlane(l, j);
             int won = 0;
-            if (lane == 0) won = (atomicCAS(&a.last[r], lj, (int)(t - 1)) == lj) ? 1 : 0;     // claim the row for this wave
+            if (lane == 0) won = (atomicCAS(&a.last[r], lj, (int)catchup_end(t)) == lj) ? 1 : 0;     // claim the row for this wave
             won = __builtin_amdgcn_readfirstlane(won);
             if (!won) continue;
-            replay_row(r, lj);
+            wave_replay_row<false>(a.table, a.m_tab, a.v_tab, r, lj, a.D, lane, st, tab);
         }
         if (base + 64LL * n_w < n_c) __syncthreads();    // (a wave of the next round must not raise any_lag while a slow one still reads it)
     }
@@ -268,7 +223,7 @@ __global__ __launch_bounds__(256) void step_head_kernel(const StepHeadArgs a, co
 // batch were made when the pool was filled, so the head builds nothing -- and the four later launches carry no sort riders.  Roles:
 //   [0, ncp)    copy: the batch image into the plan's input words, the batch's slab section by section into the plan's own buffers (every
 //               later launch reads those, untouched), n_uniq, the batch's out-of-range flag OR-ed into the plan's; one thread writes `step`
-//   the rest    the lazy-Adam catch-up over the slab's UNIQUE ids, a wave per lagging row (step_head_kernel's arithmetic): a row has one
+//   the rest    the lazy-Adam catch-up over the slab's UNIQUE ids, a wave per lagging row (adam_replay.h wave_replay_row): a row has one
 //               owner, so nobody claims it -- `last[r]` ends at t - 1 as there
 //   W16         the weight-image riders as the launch's last workgroups, as in step_head_kernel
 // Nobody waits for anybody: every role reads the pool and the slab, which nothing writes during an epoch.
@@ -321,21 +276,9 @@ __global__ __launch_bounds__(256) void step_head_prepared_kernel(const StepHeadA
     StepState st = *a.st;
     st.step = t_pre + 1;                         // (the copy's own `step` word may or may not have been written yet: not used)
     const long long t = st.step;
-    const int lane = threadIdx.x & 63, D = a.D;
+    const int lane = threadIdx.x & 63;
     const int* __restrict__ uq = sl + q.lay.uniq_ids;
     const int n_c = q.lay.n_c;
-    auto replay_row = [&](long long r, int l) {
-        for (int c = lane; c < (D >> 1); c += 64) {
-            const long long off = r * D + 2 * c;
-            const float2 p2 = *reinterpret_cast<const float2*>(a.table + off), m2 = *reinterpret_cast<const float2*>(a.m_tab + off),
-                         v2 = *reinterpret_cast<const float2*>(a.v_tab + off);
-            float p[2] = {p2.x, p2.y}, m[2] = {m2.x, m2.y}, v[2] = {v2.x, v2.y};
-            replay_elems<2>(p, m, v, (long long)l + 1, t - 1, st, tab);
-            *reinterpret_cast<float2*>(a.table + off) = make_float2(p[0], p[1]);
-            *reinterpret_cast<float2*>(a.m_tab + off) = make_float2(m[0], m[1]);
-            *reinterpret_cast<float2*>(a.v_tab + off) = make_float2(v[0], v[1]);
-        }
-    };
     const int n_w = nbk * (blockDim.x >> 6), wv = threadIdx.x >> 6;
     // Every id of the wave is resolved ONCE, lane j the wave's j-th (slab -> id -> stamp: two dependent loads paid side by side), and the
     // count U is loaded beside the ids, not in front of them: an entry behind U holds an id of [0, n_rows) left by an earlier fill -- zero
@@ -357,14 +300,14 @@ __global__ __launch_bounds__(256) void step_head_prepared_kernel(const StepHeadA
     fill_coef_table(tab, st);
     while (base < U) {
         const long long i = base + wv + (long long)lane * n_w;
-        unsigned long long todo = __ballot(i < U && l > 0 && l < t - 1);
+        unsigned long long todo = __ballot(i < U && row_owes(l, catchup_end(t)));
         while (todo != 0ull) {
             const int j = __builtin_ctzll(todo);
             todo &= todo - 1;
             const long long r = __builtin_amdgcn_readlane(id, j);
             const int lj = __builtin_amdgcn_readlane(l, j);
-            replay_row(r, lj);
-            if (lane == 0) a.last[r] = (int)(t - 1);             // (the row's only owner: no claim)
+            wave_replay_row<false>(a.table, a.m_tab, a.v_tab, r, lj, a.D, lane, st, tab);
+            if (lane == 0) a.last[r] = (int)catchup_end(t);      // (the row's only owner: no claim)
         }
         base += 64LL * n_w;
         if (base < U) resolve(base, id, l);
@@ -376,23 +319,10 @@ __global__ __launch_bounds__(256) void lazy_adam_flush_kernel(float* __restrict_
                                                               int* __restrict__ last, long long n_rows, int D, const StepState* __restrict__ stp) {
     __shared__ IdleCoef tab[COEF_TAB];
     const StepState st = *stp;
-    const long long t = st.step;
     const int sub = threadIdx.x & 31;
-    const int q = D >> 2;
     const long long hw0 = (long long)blockIdx.x * (blockDim.x >> 5) + (threadIdx.x >> 5), n_hw = (long long)gridDim.x * (blockDim.x >> 5);
     fill_coef_table(tab, st);
-    for (long long r = hw0; r < n_rows; r += n_hw) {
-        const long long l = last[r];
-        if (!(l > 0 && l < t)) continue;
-        for (int c = sub; c < q; c += 32) {
-            const long long off = r * D + 4 * c;
-            float4 p = ld4(table + off), m = ld4(m_tab + off), v = ld4(v_tab + off);
-            replay_quad(p, m, v, l + 1, t, st, tab);
-            st4(table + off, p); st4(m_tab + off, m); st4(v_tab + off, v);
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (sub == 0) last[r] = (int)t;
-    }
+    for (long long r = hw0; r < n_rows; r += n_hw) halfwave_row<ROW_FLUSH>(table, m_tab, v_tab, last, r, D, sub, st, tab);
 }
 
 // dense Adam over the flat (non-table) parameter buffer
@@ -400,67 +330,46 @@ __global__ __launch_bounds__(256) void adam_dense_kernel(float* __restrict__ p, 
                                                          const float* __restrict__ g, long long n, const StepState* __restrict__ stp,
                                                          float grad_scale) {
     const StepState st = *stp;
-    const AdamCoef c = adam_coef_now(st);
-    const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    const long long stride = (long long)gridDim.x * blockDim.x * 4;
-    for (long long i = i0; i < n; i += stride) {
-        if (i + 4 <= n) {
-            float4 pp = ld4(p + i), mm = ld4(m + i), vv = ld4(v + i);
-            adam_quad(pp, mm, vv, f4scale(ld4(g + i), grad_scale), c);
-            st4(p + i, pp); st4(m + i, mm); st4(v + i, vv);
-        } else {
-            for (long long k = i; k < n; ++k) adam_elem(p[k], m[k], v[k], g[k] * grad_scale, c);
-        }
-    }
+    dense_adam_range(p, m, v, n, blockIdx.x, gridDim.x, FlatGrad{g}, grad_scale, adam_coef_now(st));
 }
 
 __global__ void step_begin_kernel(StepState* st) { st->step += 1; st->step_done = st->step; }
 
+// torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1 (float32 tensor arithmetic)
+__device__ __forceinline__ float clip_coef(const float* __restrict__ sqnorm, float max_norm) {
+    const float c = __fdiv_rn(max_norm, __fadd_rn(__fsqrt_rn(*sqnorm), 1e-6f));
+    return c < 1.0f ? c : 1.0f;                          // (max_norm = +inf: exactly 1)
+}
+
 // One launch for the whole optimizer: blocks [0, dense_blocks) run dense Adam over the flat buffer, the rest apply the
 // lazy row Adam to the touched table rows (independent memory, so the two roles need no ordering).
+// CLIP (amid_optimizer_step_clip_f32; the norm: optim_clip.hip): the gradients are scaled by grad_scale * c, c = min(1, max_norm /
+// (sqrt(*sqnorm) + 1e-6)) read on the device; the plain step reads neither sqnorm nor max_norm.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void optimizer_step_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                              const float* __restrict__ g, long long n, int dense_blocks,
                                                              float* __restrict__ table, float* __restrict__ m_tab, float* __restrict__ v_tab,
                                                              int* __restrict__ last, const int* __restrict__ uniq_ids,
                                                              const int* __restrict__ n_uniq_p, const float* __restrict__ uniq_grad, int D,
-                                                             const StepState* __restrict__ stp, float grad_scale) {
+                                                             const StepState* __restrict__ stp, float grad_scale,
+                                                             const float* __restrict__ sqnorm, float max_norm) {
     __shared__ IdleCoef tab[COEF_TAB];
     const StepState st = *stp;
+    float gs = grad_scale;
+    if constexpr (CLIP) gs = grad_scale * clip_coef(sqnorm, max_norm);
     if ((int)blockIdx.x < dense_blocks) {
-        const AdamCoef c = adam_coef_now(st);
-        const long long stride = (long long)dense_blocks * blockDim.x * 4;
-        for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
-            if (i + 4 <= n) {
-                float4 pp = ld4(p + i), mm = ld4(m + i), vv = ld4(v + i);
-                adam_quad(pp, mm, vv, f4scale(ld4(g + i), grad_scale), c);
-                st4(p + i, pp); st4(m + i, mm); st4(v + i, vv);
-            } else {
-                for (long long k = i; k < n; ++k) adam_elem(p[k], m[k], v[k], g[k] * grad_scale, c);
-            }
-        }
+        dense_adam_range(p, m, v, n, blockIdx.x, dense_blocks, FlatGrad{g}, gs, adam_coef_now(st));
         return;
     }
-    const long long t = st.step;
     const int U = *n_uniq_p;
     const int rb = blockIdx.x - dense_blocks, n_rb = gridDim.x - dense_blocks;
     if (rb * 8 >= U) return;
     fill_coef_table(tab, st);
     const AdamCoef cnow = adam_coef_now(st);
     const int sub = threadIdx.x & 31;
-    const int q = D >> 2;
     for (int u = rb * 8 + (threadIdx.x >> 5); u < U; u += n_rb * 8) {
-        const long long r = uniq_ids[u];
-        const long long l = last[r];
-        const bool lag = (l > 0 && l < t - 1);
-        for (int c = sub; c < q; c += 32) {
-            const long long off = r * D + 4 * c;
-            float4 pp = ld4(table + off), mm = ld4(m_tab + off), vv = ld4(v_tab + off);
-            if (lag) replay_quad(pp, mm, vv, l + 1, t - 1, st, tab);
-            adam_quad(pp, mm, vv, f4scale(ld4(uniq_grad + (long long)u * D + 4 * c), grad_scale), cnow);
-            st4(table + off, pp); st4(m_tab + off, mm); st4(v_tab + off, vv);
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (sub == 0) last[r] = (int)t;
+        const auto grad = [&](int c) { return ld4(uniq_grad + (long long)u * D + 4 * c); };
+        halfwave_row<ROW_STEP>(table, m_tab, v_tab, last, uniq_ids[u], D, sub, st, tab, cnow, gs, grad);
     }
 }
 
@@ -488,7 +397,7 @@ __global__ __launch_bounds__(256) void optimizer_step_spans_kernel(float* __rest
         const long long t = st.step;
         const long long r = uniq_ids[u];
         const long long l = last[r];
-        const bool lag = (l > 0 && l < t - 1);                       // (block-uniform: one row.  The pad row, the usual owner, never lags)
+        const bool lag = row_owes(l, catchup_end(t));                // (block-uniform: one row.  The pad row, the usual owner, never lags)
         spans_partials<VEC, 4>(red, blockIdx.x, c_last, partial);
         if (lag) fill_coef_table(tab, st);
         __syncthreads();                                             // red is complete
@@ -499,8 +408,7 @@ __global__ __launch_bounds__(256) void optimizer_step_spans_kernel(float* __rest
             st4(uniq_grad + (long long)u * D + 4 * c, gs);
             const long long off = r * D + 4 * c;
             float4 pp = ld4(table + off), mm = ld4(m_tab + off), vv = ld4(v_tab + off);
-            if (lag) replay_quad(pp, mm, vv, l + 1, t - 1, st, tab);
-            adam_quad(pp, mm, vv, f4scale(gs, grad_scale), cnow);
+            row_quad_step(pp, mm, vv, gs, grad_scale, l, lag, st, tab, cnow);
             st4(table + off, pp); st4(m_tab + off, mm); st4(v_tab + off, vv);
         }
         if (threadIdx.x == 0) last[r] = (int)t;
@@ -508,41 +416,19 @@ __global__ __launch_bounds__(256) void optimizer_step_spans_kernel(float* __rest
     }
     const int bid = blockIdx.x - nch;
     if (bid < dense_blocks) {
-        const AdamCoef c = adam_coef_now(st);
-        const long long stride = (long long)dense_blocks * blockDim.x * 4;
-        for (long long i = ((long long)bid * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
-            if (i + 4 <= n) {
-                float4 pp = ld4(p + i), mm = ld4(m + i), vv = ld4(v + i);
-                adam_quad(pp, mm, vv, f4scale(ld4(g + i), grad_scale), c);
-                st4(p + i, pp); st4(m + i, mm); st4(v + i, vv);
-            } else {
-                for (long long k = i; k < n; ++k) adam_elem(p[k], m[k], v[k], g[k] * grad_scale, c);
-            }
-        }
+        dense_adam_range(p, m, v, n, bid, dense_blocks, FlatGrad{g}, grad_scale, adam_coef_now(st));
         return;
     }
-    const long long t = st.step;
     const int U = *n_uniq_p;
     const int rb = bid - dense_blocks, n_rb = gridDim.x - nch - dense_blocks;
     if (rb * 8 >= U) return;
     fill_coef_table(tab, st);
     const AdamCoef cnow = adam_coef_now(st);
     const int sub = threadIdx.x & 31;
-    const int q = D >> 2;
     for (int u = rb * 8 + (threadIdx.x >> 5); u < U; u += n_rb * 8) {
         if (seg_off[u] / SEG_CHUNK != (seg_off[u + 1] - 1) / SEG_CHUNK) continue;      // crosses chunks: a spans workgroup's (above)
-        const long long r = uniq_ids[u];
-        const long long l = last[r];
-        const bool lag = (l > 0 && l < t - 1);
-        for (int c = sub; c < q; c += 32) {
-            const long long off = r * D + 4 * c;
-            float4 pp = ld4(table + off), mm = ld4(m_tab + off), vv = ld4(v_tab + off);
-            if (lag) replay_quad(pp, mm, vv, l + 1, t - 1, st, tab);
-            adam_quad(pp, mm, vv, f4scale(ld4(uniq_grad + (long long)u * D + 4 * c), grad_scale), cnow);
-            st4(table + off, pp); st4(m_tab + off, mm); st4(v_tab + off, vv);
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (sub == 0) last[r] = (int)t;
+        const auto grad = [&](int c) { return ld4(uniq_grad + (long long)u * D + 4 * c); };
+        halfwave_row<ROW_STEP>(table, m_tab, v_tab, last, uniq_ids[u], D, sub, st, tab, cnow, grad_scale, grad);
     }
 }
 
@@ -560,6 +446,28 @@ __device__ __forceinline__ int find_id(const int* __restrict__ ids, int n, int x
     return (lo < n && ids[lo] == x) ? lo : -1;
 }
 
+// the dense gradient of the gathered optimizer: the ranks' dense parts (d0 + r * chunk_floats) summed in rank order and stored to g -- or,
+// `reduced`, g as it is: the caller all-reduced the dense gradient into it
+struct GatheredDenseGrad {
+    float* __restrict__ g; const float* d0; bool reduced; int world; long long chunk_floats;
+    __device__ __forceinline__ float4 quad(long long i) const {
+        if (reduced) return ld4(g + i);
+        float4 gg = ld4(d0 + i);
+        for (int r = 1; r < world; ++r) {
+            const float4 t = ld4(d0 + r * chunk_floats + i);
+            gg.x += t.x; gg.y += t.y; gg.z += t.z; gg.w += t.w;
+        }
+        st4(g + i, gg);
+        return gg;
+    }
+    __device__ __forceinline__ float one(long long k) const {
+        float gs = reduced ? g[k] : d0[k];
+        for (int r = 1; !reduced && r < world; ++r) gs += d0[r * chunk_floats + k];
+        g[k] = gs;
+        return gs;
+    }
+};
+
 __global__ __launch_bounds__(256) void optimizer_gathered_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                                  float* __restrict__ g, long long n, int dense_blocks,
                                                                  float* __restrict__ table, float* __restrict__ m_tab, float* __restrict__ v_tab,
@@ -569,44 +477,16 @@ __global__ __launch_bounds__(256) void optimizer_gathered_kernel(float* __restri
     __shared__ IdleCoef tab[COEF_TAB];
     const StepState st = *stp;
     if ((int)blockIdx.x < dense_blocks) {
-        const AdamCoef c = adam_coef_now(st);
-        const long long stride = (long long)dense_blocks * blockDim.x * 4;
-        const float* d0 = gathered + dense_off;
-        for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
-            if (i + 4 <= n) {
-                float4 gg;
-                if (dense_off < 0) {                                   // the dense gradient was all-reduced into g by the caller
-                    gg = ld4(g + i);
-                } else {
-                    gg = ld4(d0 + i);
-                    for (int r = 1; r < world; ++r) {
-                        const float4 t = ld4(d0 + r * chunk_floats + i);
-                        gg.x += t.x; gg.y += t.y; gg.z += t.z; gg.w += t.w;
-                    }
-                    st4(g + i, gg);
-                }
-                float4 pp = ld4(p + i), mm = ld4(m + i), vv = ld4(v + i);
-                adam_quad(pp, mm, vv, f4scale(gg, grad_scale), c);
-                st4(p + i, pp); st4(m + i, mm); st4(v + i, vv);
-            } else {
-                for (long long k = i; k < n; ++k) {
-                    float gs = dense_off < 0 ? g[k] : d0[k];
-                    for (int r = 1; dense_off >= 0 && r < world; ++r) gs += d0[r * chunk_floats + k];
-                    g[k] = gs;
-                    adam_elem(p[k], m[k], v[k], gs * grad_scale, c);
-                }
-            }
-        }
+        dense_adam_range(p, m, v, n, blockIdx.x, dense_blocks, GatheredDenseGrad{g, gathered + dense_off, dense_off < 0, world, chunk_floats}, grad_scale,
+                         adam_coef_now(st));
         return;
     }
-    const long long t = st.step;
     const int rb = blockIdx.x - dense_blocks, n_rb = gridDim.x - dense_blocks;
     const int total = world * umax;
     if (rb * 8 >= total) return;
     fill_coef_table(tab, st);
     const AdamCoef cnow = adam_coef_now(st);
     const int sub = threadIdx.x & 31;
-    const int q = D >> 2;
     for (int u = rb * 8 + (threadIdx.x >> 5); u < total; u += n_rb * 8) {
         const int r0 = u / umax, i0 = u - r0 * umax;
         const int x = ((const int*)(gathered + r0 * chunk_floats))[i0];
@@ -617,10 +497,7 @@ __global__ __launch_bounds__(256) void optimizer_gathered_kernel(float* __restri
         if (sub < world && sub != r0) j = find_id((const int*)(gathered + sub * chunk_floats), umax, x);
         const unsigned int fm = (unsigned int)(__ballot(j >= 0) >> (32 * half));
         if (fm & ((1u << r0) - 1u)) continue;                          // an earlier rank's entry applies this id
-        const long long row = x;
-        const long long l = last[row];
-        const bool lag = (l > 0 && l < t - 1);
-        for (int c = sub; c < q; c += 32) {
+        const auto grad = [&](int c) {
             float4 gg = ld4(gathered + r0 * chunk_floats + (long long)(id_rows + i0) * D + 4 * c);
             for (int r = r0 + 1; r < world; ++r) {                     // the later ranks' rows of the same id, in rank order
                 const int jr = __shfl(j, 32 * half + r);
@@ -629,14 +506,9 @@ __global__ __launch_bounds__(256) void optimizer_gathered_kernel(float* __restri
                     gg.x += tt.x; gg.y += tt.y; gg.z += tt.z; gg.w += tt.w;
                 }
             }
-            const long long off = row * D + 4 * c;
-            float4 pp = ld4(table + off), mm = ld4(m_tab + off), vv = ld4(v_tab + off);
-            if (lag) replay_quad(pp, mm, vv, l + 1, t - 1, st, tab);
-            adam_quad(pp, mm, vv, f4scale(gg, grad_scale), cnow);
-            st4(table + off, pp); st4(m_tab + off, mm); st4(v_tab + off, vv);
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (sub == 0) last[row] = (int)t;
+            return gg;
+        };
+        halfwave_row<ROW_STEP>(table, m_tab, v_tab, last, x, D, sub, st, tab, cnow, grad_scale, grad);
     }
 }
 
@@ -658,14 +530,12 @@ struct DenseAdamSink {
     __device__ __forceinline__ void quad(float* dst, float4 g) const {
         const long long off = dst - g0;
         if (off < 0 || off + 4 > n) return;                   // (a sum that is no parameter's gradient: the loss)
-        float4 pp = ld4(p + off), mm = ld4(m + off), vv = ld4(v + off);
-        adam_quad(pp, mm, vv, f4scale(g, gs), c);
-        st4(p + off, pp); st4(m + off, mm); st4(v + off, vv);
+        dense_quad_step(p, m, v, off, g, gs, c);
     }
     __device__ __forceinline__ void one(float* dst, float g) const {
         const long long off = dst - g0;
         if (off < 0 || off >= n) return;
-        adam_elem(p[off], m[off], v[off], g * gs, c);
+        dense_elem_step(p, m, v, off, g, gs, c);
     }
 };
 
@@ -740,7 +610,7 @@ __global__ __launch_bounds__(256) void grad_tail_opt_kernel(const TailOptArgs a)
                 spans_owner(c, a.seg_off, a.seg_of, a.n_sorted, SEG_CHUNK, u, c_last);
                 long long r = 0, l = 0;
                 if constexpr (APPLY) { r = a.uniq_ids[u]; l = a.last[r]; }
-                const bool lag = APPLY && (l > 0 && l < t - 1);    // (block-uniform: one row.  The pad row, the usual owner, never lags)
+                const bool lag = APPLY && row_owes(l, catchup_end(t));      // (block-uniform: one row.  The pad row, the usual owner, never lags)
                 // (the row's parameter and moments requested in front of the pieces: D / 4 <= 64 quads, one per thread of the first wave)
                 const int cq0 = threadIdx.x;
                 float4 pp0 = make_float4(0.f, 0.f, 0.f, 0.f), mm0 = pp0, vv0 = pp0;
@@ -757,8 +627,7 @@ __global__ __launch_bounds__(256) void grad_tail_opt_kernel(const TailOptArgs a)
                     if constexpr (APPLY) {
                         const long long off = r * D + 4 * cq;
                         float4 pp = pp0, mm = mm0, vv = vv0;
-                        if (lag) replay_quad(pp, mm, vv, l + 1, t - 1, st, tab);
-                        adam_quad(pp, mm, vv, f4scale(gs, a.grad_scale), cnow);
+                        row_quad_step(pp, mm, vv, gs, a.grad_scale, l, lag, st, tab, cnow);
                         st4(a.table + off, pp); st4(a.m_tab + off, mm); st4(a.v_tab + off, vv);
                     }
                 }
@@ -821,19 +690,13 @@ __global__ __launch_bounds__(256) void grad_tail_opt_kernel(const TailOptArgs a)
         AdamCoef cnow = {};
         if constexpr (APPLY) { fill_coef_table(tab, st); cnow = adam_coef_now(st); }
         const int sub = threadIdx.x & 31;
-        constexpr int q = D >> 2;
         for (int u = bid * 8 + (threadIdx.x >> 5); u < U; u += a.row_blocks * 8) {
             const int s0 = a.seg_off[u], s1 = a.seg_off[u + 1];
             if (s1 - s0 > SEG_CHUNK) continue;                     // longer than a chunk: the chunk blocks' pieces, the last chunk block's sum (above)
             // a run of at most a chunk's length lies inside one chunk or crosses ONE border: [s0, mid) and [mid, s1)
             const int mid = min(s1, (s0 / SEG_CHUNK + 1) * SEG_CHUNK);
-            long long r = 0, l = 0;
-            if constexpr (APPLY) { r = a.uniq_ids[u]; l = a.last[r]; }
-            const bool lag = APPLY && (l > 0 && l < t - 1);
-            for (int c = sub; c < q; c += 32) {
-                const long long off = r * D + 4 * c;
-                float4 pp = make_float4(0.f, 0.f, 0.f, 0.f), mm = pp, vv = pp;
-                if constexpr (APPLY) { pp = ld4(a.table + off); mm = ld4(a.m_tab + off); vv = ld4(a.v_tab + off); }      // (in flight under the run's rows)
+            // the run's sum for column quad c, written to uniq_grad (the row's parameter and moments are in flight under it: halfwave_row)
+            const auto grad = [&](int c) {
                 auto piece = [&](int e, const int e_end) {         // rows e .. e_end - 1 added in list order from zero (a chunk wave's sum), eight in flight
                     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
                     for (; e + 8 <= e_end; e += 8) {
@@ -858,16 +721,9 @@ __global__ __launch_bounds__(256) void grad_tail_opt_kernel(const TailOptArgs a)
                     gs = f4add(f4add(z, r0), r1);
                 }
                 st4(a.uniq_grad + (long long)u * D + 4 * c, gs);
-                if constexpr (APPLY) {
-                    if (lag) replay_quad(pp, mm, vv, l + 1, t - 1, st, tab);
-                    adam_quad(pp, mm, vv, f4scale(gs, a.grad_scale), cnow);
-                    st4(a.table + off, pp); st4(a.m_tab + off, mm); st4(a.v_tab + off, vv);
-                }
-            }
-            if constexpr (APPLY) {
-                __builtin_amdgcn_wave_barrier();
-                if (sub == 0) a.last[r] = (int)t;
-            }
+                return gs;
+            };
+            halfwave_row<APPLY ? ROW_STEP : ROW_SHIP>(a.table, a.m_tab, a.v_tab, a.last, APPLY ? a.uniq_ids[u] : 0, D, sub, st, tab, cnow, a.grad_scale, grad);
         }
         return;
     }
@@ -893,6 +749,13 @@ extern "C" int amid_step_begin(void* step_state, void* stream) {
     step_begin_kernel<<<1, 1, 0, (hipStream_t)stream>>>((StepState*)step_state);
     AMID_LAUNCH_CHECK();
     return AMID_OK;
+}
+
+static inline int dense_grid(long long n, int cap) {
+    long long b = (n / 4 + 255) / 256;
+    if (b < 1) b = 1;
+    if (b > cap) b = cap;
+    return (int)b;
 }
 
 static inline int rows_grid(long long n_rows_hint) {
@@ -931,10 +794,21 @@ extern "C" int amid_lazy_adam_flush_f32(float* table, float* m, float* v, int* l
 extern "C" int amid_adam_dense_f32(float* p, float* m, float* v, const float* g, long long n, float grad_scale, const void* step_state,
                                    void* stream) {
     AMID_CHECK_ARG(p && m && v && g && step_state && n > 0);
-    long long b = (n / 4 + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 2048) b = 2048;
-    adam_dense_kernel<<<(int)b, 256, 0, (hipStream_t)stream>>>(p, m, v, g, n, (const StepState*)step_state, grad_scale);
+    adam_dense_kernel<<<dense_grid(n, 2048), 256, 0, (hipStream_t)stream>>>(p, m, v, g, n, (const StepState*)step_state, grad_scale);
+    AMID_LAUNCH_CHECK();
+    return AMID_OK;
+}
+
+// the plain step (sqnorm = NULL; n > 0) and the clipped one (n >= 0: the reference's loop may hold the table alone)
+static int optimizer_step(float* p, float* m, float* v, const float* g, long long n, float* table, float* m_tab, float* v_tab, int* last,
+                          const int* uniq_ids, const int* n_uniq, int n_uniq_max, const float* uniq_grad, int D, float grad_scale,
+                          const void* step_state, bool clip, const float* sqnorm, float max_norm, void* stream) {
+    AMID_CHECK_ARG(p && m && v && g && table && m_tab && v_tab && last && uniq_ids && n_uniq && uniq_grad && step_state && D > 0 &&
+                   (D % 4) == 0 && n_uniq_max > 0 && (clip ? n >= 0 && sqnorm && max_norm >= 0.0f : n > 0));
+    const int db = dense_grid(n, 1024), rb = rows_grid(n_uniq_max);
+    const auto kernel = clip ? optimizer_step_kernel<true> : optimizer_step_kernel<false>;
+    kernel<<<db + rb, 256, 0, (hipStream_t)stream>>>(p, m, v, g, n, db, table, m_tab, v_tab, last, uniq_ids, n_uniq, uniq_grad, D,
+                                                     (const StepState*)step_state, grad_scale, sqnorm, max_norm);
     AMID_LAUNCH_CHECK();
     return AMID_OK;
 }
@@ -942,16 +816,17 @@ extern "C" int amid_adam_dense_f32(float* p, float* m, float* v, const float* g,
 extern "C" int amid_optimizer_step_f32(float* p, float* m, float* v, const float* g, long long n, float* table, float* m_tab, float* v_tab,
                                        int* last, const int* uniq_ids, const int* n_uniq, int n_uniq_max, const float* uniq_grad, int D,
                                        float grad_scale, const void* step_state, void* stream) {
-    AMID_CHECK_ARG(p && m && v && g && n > 0 && table && m_tab && v_tab && last && uniq_ids && n_uniq && uniq_grad && step_state && D > 0 &&
-                   (D % 4) == 0 && n_uniq_max > 0);
-    long long db = (n / 4 + 255) / 256;
-    if (db < 1) db = 1;
-    if (db > 1024) db = 1024;
-    const int rb = rows_grid(n_uniq_max);
-    optimizer_step_kernel<<<(int)db + rb, 256, 0, (hipStream_t)stream>>>(p, m, v, g, n, (int)db, table, m_tab, v_tab, last, uniq_ids, n_uniq,
-                                                                          uniq_grad, D, (const StepState*)step_state, grad_scale);
-    AMID_LAUNCH_CHECK();
-    return AMID_OK;
+    return optimizer_step(p, m, v, g, n, table, m_tab, v_tab, last, uniq_ids, n_uniq, n_uniq_max, uniq_grad, D, grad_scale, step_state, false,
+                          nullptr, 0.0f, stream);
+}
+
+// amid_optimizer_step_f32 whose gradients are scaled by grad_scale * c, c = torch's clip coefficient of *sqnorm (amid_grad_sqnorm_f32,
+// optim_clip.hip) and max_norm, read on the device
+extern "C" int amid_optimizer_step_clip_f32(float* p, float* m, float* v, const float* g, long long n, float* table, float* m_tab, float* v_tab,
+                                            int* last, const int* uniq_ids, const int* n_uniq, int n_uniq_max, const float* uniq_grad, int D,
+                                            float grad_scale, const void* step_state, const float* sqnorm, float max_norm, void* stream) {
+    return optimizer_step(p, m, v, g, n, table, m_tab, v_tab, last, uniq_ids, n_uniq, n_uniq_max, uniq_grad, D, grad_scale, step_state, true,
+                          sqnorm, max_norm, stream);
 }
 
 extern "C" int amid_optimizer_step_gathered_f32(float* p, float* m, float* v, float* g, long long n, float* table, float* m_tab, float* v_tab,
@@ -965,11 +840,8 @@ extern "C" int amid_optimizer_step_gathered_f32(float* p, float* m, float* v, fl
                                   : (dense_off >= (long long)(id_rows + umax) * D && (dense_off % 4) == 0 && chunk_floats >= dense_off + n)));
     // lane r of a half-wave hands rank r's search result to the column loop, where only the first D / 4 lanes are alive
     if (D < 4 * world) return AMID_ERR_UNSUPPORTED;
-    long long db = (n / 4 + 255) / 256;
-    if (db < 1) db = 1;
-    if (db > 1024) db = 1024;
-    const int rb = rows_grid((long long)world * umax);
-    optimizer_gathered_kernel<<<(int)db + rb, 256, 0, (hipStream_t)stream>>>(p, m, v, g, n, (int)db, table, m_tab, v_tab, last, gathered, world,
+    const int db = dense_grid(n, 1024), rb = rows_grid((long long)world * umax);
+    optimizer_gathered_kernel<<<db + rb, 256, 0, (hipStream_t)stream>>>(p, m, v, g, n, db, table, m_tab, v_tab, last, gathered, world,
                                                                               umax, chunk_floats, id_rows, dense_off, D, sentinel,
                                                                               (const StepState*)step_state, grad_scale);
     AMID_LAUNCH_CHECK();
@@ -1171,13 +1043,10 @@ extern "C" int amid_optimizer_step_spans_f32(float* p, float* m, float* v, const
     AMID_CHECK_ARG(p && m && v && g && n > 0 && table && m_tab && v_tab && last && uniq_ids && n_uniq && uniq_grad && step_state &&
                    n_uniq_max > 0 && seg_off && seg_of && n_sorted > 0 && workspace);
     if (!(D == 64 || D == 128 || D == 256)) return AMID_ERR_UNSUPPORTED;
-    long long db = (n / 4 + 255) / 256;
-    if (db < 1) db = 1;
-    if (db > 1024) db = 1024;
-    const int rb = rows_grid(n_uniq_max);
+    const int db = dense_grid(n, 1024), rb = rows_grid(n_uniq_max);
     const int nch = (n_sorted + SEG_CHUNK - 1) / SEG_CHUNK;
 #define AMID_OPT_LAUNCH(VEC)                                                                                                              \
-    optimizer_step_spans_kernel<VEC><<<nch + (int)db + rb, 256, 0, (hipStream_t)stream>>>(p, m, v, g, n, (int)db, table, m_tab, v_tab, last, uniq_ids, \
+    optimizer_step_spans_kernel<VEC><<<nch + db + rb, 256, 0, (hipStream_t)stream>>>(p, m, v, g, n, db, table, m_tab, v_tab, last, uniq_ids, \
                                                                                           n_uniq, uniq_grad, (const StepState*)step_state, grad_scale, \
                                                                                           seg_off, seg_of, n_sorted, (const float*)workspace, nch);
     if (D == 64) { AMID_OPT_LAUNCH(1) } else if (D == 128) { AMID_OPT_LAUNCH(2) } else { AMID_OPT_LAUNCH(4) }

@@ -184,4 +184,119 @@ __device__ __forceinline__ void replay_quad(float4& p, float4& m, float4& v, lon
     p = make_float4(pp[0], pp[1], pp[2], pp[3]); m = make_float4(mm[0], mm[1], mm[2], mm[3]); v = make_float4(vv[0], vv[1], vv[2], vv[3]);
 }
 
+// ---- the roles the optimizer kernels are built from (adam.hip, embed.hip's folded gather) ------------------------------------------------
+// A row's stamp last[r] = l says: every step through l is in the row (l = 0: never touched, m = v = 0, every update is exactly 0, nothing to
+// replay).  In front of the real step t a row must hold the steps through t - 1; a flush brings it through t itself.  A row stamped l owes
+// the zero-gradient steps l + 1 .. end, and ends stamped `end` after a catch-up, t after the real step.
+// (The role functions take plain pointers: a kernel whose own parameters are __restrict__ keeps that knowledge through the inlining, and
+// one that holds its pointers in a struct -- the gradient tail -- is not given a promise it never made: with __restrict__ here its Adam
+// steps were scheduled differently and cfg4's step took 0.0005 ms longer, profiles/adam_roles.md.)
+__device__ __forceinline__ long long catchup_end(long long t) { return t - 1; }
+__device__ __forceinline__ long long flush_end(long long t) { return t; }
+// (the stamp as the caller holds it, int or long long, and both by reference: inlined, the test then compiles as it did written out at the
+// call sites -- by value it cost embed.hip's folded gather 23 more exec-mask branches, profiles/adam_roles.md)
+template <class Stamp>
+__device__ __forceinline__ bool row_owes(const Stamp& l, const long long& end) { return l > 0 && l < end; }
+template <int N>
+__device__ __forceinline__ void replay_owed_elems(float (&p)[N], float (&m)[N], float (&v)[N], long long l, long long end, const StepState& st,
+                                                  const IdleCoef* tab) {
+    replay_elems<N>(p, m, v, l + 1, end, st, tab);
+}
+__device__ __forceinline__ void replay_owed_quad(float4& p, float4& m, float4& v, long long l, long long end, const StepState& st,
+                                                 const IdleCoef* tab) {
+    replay_quad(p, m, v, l + 1, end, st, tab);
+}
+
+// dense step of the quad at offset i / of the element at k, with the gradient g scaled by gs
+__device__ __forceinline__ void dense_quad_step(float* p, float* m, float* v, long long i, float4 g, float gs,
+                                                const AdamCoef& c) {
+    float4 pp = ld4(p + i), mm = ld4(m + i), vv = ld4(v + i);
+    adam_quad(pp, mm, vv, f4scale(g, gs), c);
+    st4(p + i, pp); st4(m + i, mm); st4(v + i, vv);
+}
+__device__ __forceinline__ void dense_elem_step(float* p, float* m, float* v, long long k, float g, float gs,
+                                                const AdamCoef& c) {
+    adam_elem(p[k], m[k], v[k], g * gs, c);
+}
+
+// dense Adam over [0, n) by block `bid` of `nblocks`: a grid-stride loop over quads, the last n % 4 elements one by one.  grad.quad(i) /
+// grad.one(k): the gradient at quad i / element k (FlatGrad: read from a flat buffer; the gathered optimizer's: summed over the ranks)
+struct FlatGrad {
+    const float* __restrict__ g;
+    __device__ __forceinline__ float4 quad(long long i) const { return ld4(g + i); }
+    __device__ __forceinline__ float one(long long k) const { return g[k]; }
+};
+template <class Grad>
+__device__ __forceinline__ void dense_adam_range(float* p, float* m, float* v, long long n, long long bid,
+                                                 long long nblocks, const Grad& grad, float gs, const AdamCoef& c) {
+    const long long stride = nblocks * blockDim.x * 4;
+    for (long long i = (bid * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+        if (i + 4 <= n) dense_quad_step(p, m, v, i, grad.quad(i), gs, c);
+        else for (long long k = i; k < n; ++k) dense_elem_step(p, m, v, k, grad.one(k), gs, c);
+    }
+}
+
+// the real step t = st.step of a row's quad already in registers: what the row owes (lag = row_owes(l, catchup_end(t))), then the step
+__device__ __forceinline__ void row_quad_step(float4& p, float4& m, float4& v, float4 g, float gs, long long l, bool lag, const StepState& st,
+                                              const IdleCoef* tab, const AdamCoef& cnow) {
+    if (lag) replay_owed_quad(p, m, v, l, catchup_end(st.step), st, tab);
+    adam_quad(p, m, v, f4scale(g, gs), cnow);
+}
+
+// A half-wave (sub = its lane, 0 .. 31) on row r, a quad per lane and round.  grad(c): the gradient of column quad c, called AFTER the loads
+// of the row's parameter and moments are issued, so that they are in flight under whatever it does.
+//   ROW_STEP     what the row owes, then the real step t with grad(c); stamp t
+//   ROW_CATCHUP  what the row owes in front of step t, nothing for a row that owes nothing; stamp t - 1
+//   ROW_FLUSH    the same through step t; stamp t
+//   ROW_SHIP     nothing is applied: grad(c) alone runs (it stores what it sums)
+enum RowMode { ROW_STEP, ROW_CATCHUP, ROW_FLUSH, ROW_SHIP };
+struct NoGrad { __device__ __forceinline__ float4 operator()(int) const { return make_float4(0.f, 0.f, 0.f, 0.f); } };
+template <RowMode MODE, class Grad = NoGrad>
+__device__ __forceinline__ void halfwave_row(float* table, float* m_tab, float* v_tab, int* last,
+                                             long long r, int D, int sub, const StepState& st, const IdleCoef* tab, const AdamCoef& cnow = AdamCoef{},
+                                             float gs = 1.0f, const Grad& grad = Grad{}) {
+    if constexpr (MODE == ROW_SHIP) {
+        for (int c = sub; c < (D >> 2); c += 32) grad(c);
+    } else {
+        const long long t = st.step, end = MODE == ROW_FLUSH ? flush_end(t) : catchup_end(t);
+        const long long l = last[r];
+        const bool lag = row_owes(l, end);
+        if (MODE != ROW_STEP && !lag) return;
+        for (int c = sub; c < (D >> 2); c += 32) {
+            const long long off = r * D + 4 * c;
+            float4 p = ld4(table + off), m = ld4(m_tab + off), v = ld4(v_tab + off);
+            if constexpr (MODE == ROW_STEP) row_quad_step(p, m, v, grad(c), gs, l, lag, st, tab, cnow);
+            else replay_owed_quad(p, m, v, l, end, st, tab);
+            st4(table + off, p); st4(m_tab + off, m); st4(v_tab + off, v);
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (sub == 0) last[r] = MODE == ROW_STEP ? (int)t : (int)end;
+    }
+}
+
+// A wave (lane = 0 .. 63) replays what row r, stamped l, owes in front of step t = st.step: two elements per lane -- a replay is a chain of
+// dependent steps bound by the quarter-rate sqrt / rcp, the fewer elements a lane carries the shorter the chain.  The caller stamps the row.
+// NT: non-temporal loads, for a launch in which a lagging row is read once per step and the tables are far larger than the caches (the
+// stress's catch-up launch 140.5 -> 136.7 us)
+template <bool NT>
+__device__ __forceinline__ void wave_replay_row(float* table, float* m_tab, float* v_tab, long long r, long long l, int D, int lane,
+                                                const StepState& st, const IdleCoef* tab) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    for (int c = lane; c < (D >> 1); c += 64) {
+        const long long off = r * D + 2 * c;
+        f2 pn, mn, vn;
+        if constexpr (NT) {
+            pn = __builtin_nontemporal_load((const f2*)(table + off)); mn = __builtin_nontemporal_load((const f2*)(m_tab + off));
+            vn = __builtin_nontemporal_load((const f2*)(v_tab + off));
+        } else {
+            pn = *(const f2*)(table + off); mn = *(const f2*)(m_tab + off); vn = *(const f2*)(v_tab + off);
+        }
+        float p[2] = {pn[0], pn[1]}, m[2] = {mn[0], mn[1]}, v[2] = {vn[0], vn[1]};
+        replay_owed_elems<2>(p, m, v, l, catchup_end(st.step), st, tab);
+        *reinterpret_cast<float2*>(table + off) = make_float2(p[0], p[1]);
+        *reinterpret_cast<float2*>(m_tab + off) = make_float2(m[0], m[1]);
+        *reinterpret_cast<float2*>(v_tab + off) = make_float2(v[0], v[1]);
+    }
+}
+
 }  // namespace amid

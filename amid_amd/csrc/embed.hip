@@ -183,8 +183,8 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const float* __restrict_
     unsigned long long seed = 0;
     unsigned step = 0;
     if (train) { seed = rng->seed; step = (unsigned)rng->step; }
-    // last != nullptr: the lazy-Adam catch-up folded into the gather.  A row whose stamp lags (0 < last < t - 1) owes zero-gradient Adam
-    // steps last + 1 .. t - 1 (adam.hip): they are replayed HERE, in registers, for the value the forward reads -- nothing is written;
+    // last != nullptr: the lazy-Adam catch-up folded into the gather.  A row whose stamp lags owes zero-gradient Adam steps (adam_replay.h:
+    // row_owes, catchup_end): they are replayed HERE, in registers, for the value the forward reads -- nothing is written;
     // the optimizer launch of this step, which visits exactly the rows that were gathered, replays the same steps again (the same bits:
     // adam_replay.h) in front of the real step and stamps the row.  No launch of its own, no ordering between workgroups.
     StepState stv = {};
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const float* __restrict_
                     else r += M;
                 }
                 const int l = last[idx_all[r]];
-                if (l > 0 && l < t_now - 1) mine_lag = true;
+                if (row_owes(l, catchup_end(t_now))) mine_lag = true;
             }
         }
         any_lag = __syncthreads_or(mine_lag ? 1 : 0) != 0;
@@ -275,9 +275,9 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const float* __restrict_
                 if constexpr (FOLD) if (any_lag) {
 #pragma unroll
                     for (int u = 0; u < RIF; ++u) {
-                        if (u0 + u < n_here && lst[u] > 0 && lst[u] < t_now - 1) {      // (uniform over the half-wave: it shares the row)
+                        if (u0 + u < n_here && row_owes(lst[u], catchup_end(t_now))) {      // (uniform over the half-wave: it shares the row)
                             float4 mq = ld4(m_tab + src[u] * D + 4 * c), vq = ld4(v_tab + src[u] * D + 4 * c);
-                            replay_quad(v[u], mq, vq, (long long)lst[u] + 1, t_now - 1, stv, ctab);
+                            replay_owed_quad(v[u], mq, vq, lst[u], catchup_end(t_now), stv, ctab);
                         }
                     }
                 }

@@ -273,10 +273,11 @@ def test_dense_adam_matches_torch_op_order(L):
         assert float((pd.cpu() - P["w"]).abs().max()) < 1e-6, t
 
 
-@pytest.mark.parametrize("by_position", [False, True])
+@pytest.mark.parametrize("by_position", [False, True, None])
 def test_lazy_adam_equals_dense_adam_with_idle_rows(L, by_position):
     """Rows touched at some steps and idle at others must follow the dense trajectory.
-    by_position: catch-up driven by the raw index list (duplicates included) instead of the unique list."""
+    by_position: catch-up driven by the raw index list (duplicates included) instead of the unique list; None: no catch-up launch at all --
+    amid_lazy_adam_apply_f32 itself replays what a lagging row owes in front of the real step (checked on the rows it applied)."""
     g = torch.Generator().manual_seed(11)
     n_rows, D, steps = 40, 64, 30
     tab0 = torch.randn(n_rows, D, generator=g)
@@ -295,7 +296,9 @@ def test_lazy_adam_equals_dense_adam_with_idle_rows(L, by_position):
         st = step_state(L, 0, t, lr=5e-3)
         ud, gd = dev(touched.int()), dev(grows)
         nu = torch.tensor([touched.numel()], dtype=torch.int32, device="cuda")
-        if by_position:
+        if by_position is None:
+            pass
+        elif by_position:
             pos = touched[torch.randint(0, touched.numel(), (3 * touched.numel() + 5,), generator=g)]       # duplicates, any order
             pos = torch.cat((pos, touched)).int().cuda()
             L.call("amid_lazy_adam_catchup_positions_f32", tab.data_ptr(), m.data_ptr(), v.data_ptr(), last.data_ptr(), pos.data_ptr(),
@@ -305,16 +308,55 @@ def test_lazy_adam_equals_dense_adam_with_idle_rows(L, by_position):
                    n_rows, D, st.data_ptr(), stream())
         torch.cuda.synchronize()
         # the rows about to be gathered must already equal the dense trajectory after step t-1
-        assert float((tab.cpu()[touched] - P["t"][touched]).abs().max()) < 2e-6, ("pre-gather", t)
+        if by_position is not None:
+            assert float((tab.cpu()[touched] - P["t"][touched]).abs().max()) < 2e-6, ("pre-gather", t)
         opt.step(P, {"t": dense})
         L.call("amid_lazy_adam_apply_f32", tab.data_ptr(), m.data_ptr(), v.data_ptr(), last.data_ptr(), ud.data_ptr(), nu.data_ptr(),
                n_rows, gd.data_ptr(), 1.0, D, st.data_ptr(), stream())
         torch.cuda.synchronize()
+        if by_position is None:
+            assert float((tab.cpu()[touched] - P["t"][touched]).abs().max()) < 2e-6, ("applied", t)
     st = step_state(L, 0, steps, lr=5e-3)
     L.call("amid_lazy_adam_flush_f32", tab.data_ptr(), m.data_ptr(), v.data_ptr(), last.data_ptr(), n_rows, D, st.data_ptr(), stream())
     torch.cuda.synchronize()
     assert float((tab.cpu() - P["t"]).abs().max()) < 2e-6
     assert int(last.min().item()) in (0, steps)
+
+
+def test_optimizer_step_spans_dense_tail_and_lagging_rows_follow_dense_adam(L):
+    """amid_optimizer_step_spans_f32 called directly on a list without chunk-crossing runs (one entry per id, a single chunk: no spans
+    workgroup owns anything, the workspace is never read): its dense role on n = 4099 floats (the scalar tail: the engine's flat buffer is
+    always a multiple of four) and its row role on rows that return after three idle steps, against orc.DenseAdam.  Bars: those of
+    test_dense_adam_matches_torch_op_order (1e-6) and test_lazy_adam_equals_dense_adam_with_idle_rows (2e-6)."""
+    g = torch.Generator().manual_seed(21)
+    n, n_rows, D, lr = 4099, 9, 64, 5e-3
+    p0, tab0 = torch.randn(n, generator=g), torch.randn(n_rows, D, generator=g)
+    P = {"w": p0.clone(), "t": tab0.clone()}
+    opt = orc.DenseAdam(P, lr=lr)
+    pd, md, vd = dev(p0.clone()), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
+    tab, m, v = dev(tab0.clone()), torch.zeros(n_rows, D, device="cuda"), torch.zeros(n_rows, D, device="cuda")
+    last = torch.zeros(n_rows, dtype=torch.int32, device="cuda")
+    ws = torch.zeros(16 * D, device="cuda")
+    for t in range(1, 6):
+        ids = torch.tensor([0, 2, 3, 5, 8] if t in (1, 5) else [0, 3, 8])             # rows 2 and 5: stamped 1, back at step 5
+        gw, grows = torch.randn(n, generator=g), torch.randn(ids.numel(), D, generator=g)
+        dense = torch.zeros(n_rows, D)
+        dense[ids] = grows
+        opt.step(P, {"w": gw, "t": dense})
+        U = ids.numel()
+        ud, gd, gwd = dev(ids.int()), dev(grows), dev(gw)
+        nu = torch.tensor([U], dtype=torch.int32, device="cuda")
+        seg_off, seg_of = dev(torch.arange(U + 1, dtype=torch.int32)), dev(torch.arange(U, dtype=torch.int32))
+        st = step_state(L, 0, t, lr=lr)
+        if t == 5:
+            assert last.cpu()[[2, 5]].tolist() == [1, 1]
+        L.call("amid_optimizer_step_spans_f32", pd.data_ptr(), md.data_ptr(), vd.data_ptr(), gwd.data_ptr(), n, tab.data_ptr(), m.data_ptr(),
+               v.data_ptr(), last.data_ptr(), ud.data_ptr(), nu.data_ptr(), U, gd.data_ptr(), D, 1.0, st.data_ptr(), seg_off.data_ptr(),
+               seg_of.data_ptr(), U, ws.data_ptr(), stream())
+        torch.cuda.synchronize()
+        assert float((pd.cpu() - P["w"]).abs().max()) < 1e-6, t
+        assert float((tab.cpu()[ids] - P["t"][ids]).abs().max()) < 2e-6, t
+        assert bool((last.cpu()[ids] == t).all())
 
 
 # ---------------------------------------------------------------------------------------------
