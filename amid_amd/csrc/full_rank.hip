@@ -21,18 +21,17 @@
 // the list.
 #include <algorithm>
 #include "head_parts.h"
+#include "topk_list.h"
 
 namespace amid {
 
 #pragma clang fp contract(off)
 
-constexpr int FR_THREADS = 256;
 constexpr int FR_TILE = 256;            // candidates per tile: one per thread
 constexpr int FR_UCH = 1024;            // users per count launch (LDS counters)
 constexpr int FR_UB = 8;                // users per top-K workgroup
 constexpr int FR_GRID = 512;            // persistent workgroups of the count / item-half launches
 constexpr int FR_TOPK_WGS = 1024;       // target workgroups of the top-K launch
-constexpr int FR_ID_NONE = 0x7fffffff;  // an empty list slot (sorts after every candidate)
 
 struct FrArgs {
     const float* u; long long u_dom_stride;     // user b's vector: u + domain(b) * u_dom_stride + b * D
@@ -220,65 +219,12 @@ __global__ __launch_bounds__(FR_THREADS) void fr_items_kernel(const FrArgs a) {
     }
 }
 
-// (s1, i1) ranks before (s2, i2): larger score, ties to the lower id
-__device__ __forceinline__ bool fr_before(float s1, int i1, float s2, int i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
-
-struct FrList { float* s; int* id; int* n; };          // one running best-K list in LDS
-struct FrScratch { float* s; int* id; int* wcnt; };    // merge buffer [512] scores, [512] ids; per-wave counts [4]
-
-// Offer one candidate per thread (cand: it takes part) to the list; every thread of the workgroup calls this.  Newcomers that beat the
-// list's K-th entry (or join a list not yet full) go behind the list in the merge buffer, list + newcomers are sorted (bitonic over the
-// next power of two, at most 512 entries) and the first K stay.
-__device__ __forceinline__ void fr_offer(const FrList& L, const FrScratch& S, int K, bool cand, float s, int id) {
-    const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
-    const int n = *L.n;
-    bool beat = cand;
-    if (cand && n == K) beat = fr_before(s, id, L.s[K - 1], L.id[K - 1]);
-    const unsigned long long m = __ballot(beat);
-    if (lane == 0) S.wcnt[w] = __popcll(m);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int v = 0; v < FR_THREADS / 64; ++v) { off += v < w ? S.wcnt[v] : 0; tot += S.wcnt[v]; }
-    __syncthreads();                                           // (every wave has read the counts before the next call writes them)
-    if (tot == 0) return;                                      // (uniform)
-    const int total = n + tot;
-    int size = 2;
-    while (size < total) size <<= 1;
-    if (beat) {
-        const int slot = n + off + __popcll(m & ((1ull << lane) - 1ull));
-        S.s[slot] = s; S.id[slot] = id;
-    }
-    for (int i = tid; i < size; i += FR_THREADS) {
-        if (i < n) { S.s[i] = L.s[i]; S.id[i] = L.id[i]; }
-        else if (i >= total) { S.s[i] = -INFINITY; S.id[i] = FR_ID_NONE; }
-    }
-    __syncthreads();
-    for (int k = 2; k <= size; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (size >> 1); t += FR_THREADS) {
-                const int i = 2 * j * (t / j) + (t % j), l = i + j;
-                const float sa = S.s[i], sb = S.s[l];
-                const int ia = S.id[i], ib = S.id[l];
-                const bool first = (i & k) == 0;               // this run ends up best-first
-                if (first ? fr_before(sb, ib, sa, ia) : fr_before(sa, ia, sb, ib)) {
-                    S.s[i] = sb; S.s[l] = sa; S.id[i] = ib; S.id[l] = ia;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    const int keep = min(K, total);
-    for (int i = tid; i < keep; i += FR_THREADS) { L.s[i] = S.s[i]; L.id[i] = S.id[i]; }
-    if (tid == 0) *L.n = keep;
-    __syncthreads();
-}
 
 // LDS (4-byte words): lists [FR_UB][K] scores | [FR_UB][K] ids | n [FR_UB] | merge [512] scores | [512] ids | wcnt [4] | ex [FR_TILE] |
 // tile ids [FR_TILE] (8-byte)
 __host__ __device__ inline size_t fr_topk_lds_bytes(int K) {
     return (size_t)4 * (2 * FR_UB * K + FR_UB + 2 * 512 + 4 + FR_TILE) + 8 * FR_TILE;
 }
-__host__ __device__ inline size_t fr_merge_lds_bytes(int K) { return (size_t)4 * (2 * K + 4 + 2 * 512 + 4); }
 
 template <int HID>
 __global__ __launch_bounds__(FR_THREADS) void fr_topk_kernel(const FrArgs a) {
@@ -347,34 +293,7 @@ __global__ __launch_bounds__(FR_THREADS) void fr_topk_kernel(const FrArgs a) {
 
 __global__ __launch_bounds__(FR_THREADS) void fr_merge_kernel(const FrArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int K = a.K, tid = threadIdx.x, b = blockIdx.x;
-    float* ls = sm;
-    int* li = reinterpret_cast<int*>(ls + K);
-    int* ln = li + K;
-    FrScratch S;
-    S.s = reinterpret_cast<float*>(ln + 4);
-    S.id = reinterpret_cast<int*>(S.s + 512);
-    S.wcnt = S.id + 512;
-    if (tid == 0) *ln = 0;
-    __syncthreads();
-    const FrList L{ls, li, ln};
-    const long long E = (long long)a.n_ranges * K;
-    for (long long e0 = 0; e0 < E; e0 += FR_THREADS) {
-        const long long e = e0 + tid;
-        float s = -INFINITY;
-        int id = FR_ID_NONE;
-        if (e < E) {
-            const long long r = e / K, k = e - r * K;
-            const long long o = (r * a.B + b) * K + k;
-            s = a.part_s[o]; id = a.part_i[o];
-        }
-        fr_offer(L, S, K, id != FR_ID_NONE, s, id);
-    }
-    const int n = *ln;
-    for (int k = tid; k < K; k += FR_THREADS) {
-        a.out_ids[(long long)b * K + k] = k < n ? (long long)li[k] : -1;
-        a.out_s[(long long)b * K + k] = k < n ? ls[k] : -INFINITY;
-    }
+    fr_merge_ranges(sm, a.K, a.n_ranges, a.B, blockIdx.x, a.part_s, a.part_i, a.out_ids, a.out_s);
 }
 
 #pragma clang fp contract(fast)

@@ -17,6 +17,7 @@ Memory layout (all fp32, resident in HBM for the life of the engine):
 from __future__ import annotations
 
 import ctypes
+import types
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -1746,6 +1747,104 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         lib().call("amid_topk_f32", u.data_ptr(), stride, domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel(), ptr(own),
                    ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer().values(), self.D, self.hid, int(k),
                    1 if exclude_history else 0, ws.data_ptr(), pl.err.data_ptr(), ids.data_ptr(), scores.data_ptr(), self.s)
+
+    # ------------------------------------------------------------------ the encode / score split and neighbours (csrc/neighbors.hip)
+    def encode_epoch(self, pl: SasrecPlan, packed: torch.Tensor, use_graph: bool = True) -> torch.Tensor:
+        """The vector topk_epoch scores for every row of `packed` ([n, in_words] int64: pack_epoch's images, resident in HBM), as
+        [n, 1, B, D] float32 on the device (enqueue_user_vectors' own-domain vectors; isItC: the mixed ones) or [n, 2, B, D] (the
+        forward's vectors of both domains where the evaluation is not fused: row b's is [domain(b) != 0]).  The lazy table flushed and the
+        weight images built once, then per batch one device copy of the image, one graph replay of enqueue_user_vectors (use_graph=False:
+        the same launches, eagerly) and one device copy out.  Nothing is read back."""
+        if packed.dtype != torch.int64 or packed.dim() != 2 or packed.shape[1] != pl.in_words:
+            raise ValueError(f"encode_epoch takes [n, {pl.in_words}] int64 batch images (pack_epoch)")
+        if self.table_m is not None:
+            self.flush_table()
+        L = lib()
+        n, B, D = packed.shape[0], pl.shape.B, self.D
+        fused = self.eval_fused_ok(pl)
+        with torch.cuda.stream(self.stream):
+            if fused:
+                self._enqueue_eval_images(pl)
+        if use_graph and getattr(pl, "enc_graph", None) is None:
+            with torch.cuda.stream(self.stream):
+                pl.in_pack.copy_(packed[0], non_blocking=True)
+                self.enqueue_user_vectors(pl)                # warm-up outside capture (LDS attributes, lazy buffers, images)
+            self.sync()
+            L.call("amid_graph_capture_begin", self.s)
+            try:
+                self.enqueue_user_vectors(pl, build_images=False)
+            finally:
+                out = ctypes.c_void_p()
+                L.call("amid_graph_capture_end", self.s, ctypes.byref(out))
+            pl.enc_graph = out.value
+        two = not fused                                      # enqueue_user_vectors' rule: the forward's [2, B, D] where the evaluation is not fused
+        raw = torch.empty(n, 2 if two else 1, B, D, dtype=torch.float32, device=self.device)
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            for i in range(n):
+                pl.in_pack.copy_(packed[i], non_blocking=True)
+                if use_graph:
+                    L.call("amid_graph_launch", pl.enc_graph, self.s)
+                    u = pl.u if two else pl.ev_u
+                else:
+                    u, stride = self.enqueue_user_vectors(pl, build_images=False)
+                    assert (stride != 0) == two
+                raw[i].view(-1).copy_(u.reshape(-1)[:raw[i].numel()], non_blocking=True)
+        return raw
+
+    def enqueue_topk_vectors(self, u: torch.Tensor, domain: torch.Tensor, pools, history: Optional[torch.Tensor], k: int,
+                             ids: torch.Tensor, scores: torch.Tensor, err: torch.Tensor) -> None:
+        """amid_topk_f32 on caller-supplied vectors u [B, D] (u_dom_stride = 0; any B): the k best candidates of every row's domain pool,
+        minus the ids of history [B, T] (int64; amid_own_from_seq_i64 forms the sets on the device) when given.  err: [1] int32 flags.
+        Nothing is synchronised."""
+        L, B = lib(), u.shape[0]
+        p1, p2 = pools
+        ws = self._full_rank_workspace(B, p1.numel(), p2.numel(), int(k))
+        own = own_off = rows = None
+        if history is not None:
+            T = history.shape[1]
+            with torch.cuda.stream(self.stream):
+                own = torch.empty(B * T, dtype=torch.int64, device=self.device)
+                own_off = torch.empty(B + 1, dtype=torch.int32, device=self.device)
+                cnt = torch.empty(B, dtype=torch.int32, device=self.device)
+                rows = torch.arange(B, dtype=torch.int32, device=self.device)
+            L.call("amid_own_from_seq_i64", history.data_ptr(), history.data_ptr(), domain.data_ptr(), B, T, cnt.data_ptr(), own.data_ptr(),
+                   own_off.data_ptr(), self.s)
+        ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
+        L.call("amid_topk_f32", u.data_ptr(), 0, domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel(), ptr(own),
+               ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer().values(), self.D, self.hid, int(k),
+               0 if history is None else 1, ws.data_ptr(), err.data_ptr(), ids.data_ptr(), scores.data_ptr(), self.s)
+
+    NEIGHBOR_METRICS = {"dot": 0, "cosine": 1}
+
+    def flags_holder(self):
+        """A [1] int32 flag word for launches that belong to no plan (check_index_error takes it like a plan)."""
+        if getattr(self, "_flag_holder", None) is None:
+            with torch.cuda.stream(self.stream):
+                self._flag_holder = types.SimpleNamespace(err=torch.zeros(1, dtype=torch.int32, device=self.device))
+        return self._flag_holder
+
+    def enqueue_neighbors(self, queries: torch.Tensor, base: torch.Tensor, pool: Optional[torch.Tensor], metric: str, k: int,
+                          exclude_self: bool, ids: torch.Tensor, scores: torch.Tensor, err: torch.Tensor) -> None:
+        """amid_neighbors_f32 on the engine's stream: queries [Q] int64 (rows of base) or [Q, D] float32 vectors against the rows `pool`
+        (sorted unique int64, None: every row) of base [N, D] (contiguous float32, D 64 / 128); ids [Q, k] int64, scores [Q, k].
+        Nothing is synchronised."""
+        by_id = queries.dtype == torch.int64
+        Q, (N, D) = queries.shape[0], base.shape
+        n_cand = N if pool is None else pool.numel()
+        nbytes = int(lib().value("amid_neighbors_workspace_bytes", Q, n_cand, D, int(k)))
+        if nbytes < 0:
+            raise ValueError(f"neighbors: bad sizes Q {Q}, candidates {n_cand}, D {D}, k {k}")
+        ws = getattr(self, "_nb_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            if ws is not None:
+                ws.record_stream(self.stream)
+            with torch.cuda.stream(self.stream):
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._nb_ws = ws
+        lib().call("amid_neighbors_f32", None if by_id else queries.data_ptr(), queries.data_ptr() if by_id else None, Q, base.data_ptr(), N, D,
+                   None if pool is None else pool.data_ptr(), n_cand, self.NEIGHBOR_METRICS[metric], int(k), 1 if exclude_self else 0,
+                   ws.data_ptr(), err.data_ptr(), ids.data_ptr(), scores.data_ptr(), self.s)
 
     # ------------------------------------------------------------------ parameter interchange
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:

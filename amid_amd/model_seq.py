@@ -493,6 +493,123 @@ class SASRec(nn.Module):
         eng.check_index_error(pl)
         return ids, scores
 
+    # ---- the encode / score split and neighbours over the embedding spaces (csrc/neighbors.hip)
+    @torch.no_grad()
+    def encode_users(self, users: Dict[str, torch.Tensor], use_graph: bool = True) -> torch.Tensor:
+        """The vectors recommend_all scores, taken out: users as recommend_all takes them; returns [n, B, D] float32 on the device, row
+        (i, b) the own-domain vector of that row (for an isItC model the mixed vector) -- recommend_from_vectors on it gives
+        recommend_all's rows bit for bit.  One graph replay a batch (SasrecEngine.encode_epoch; use_graph=False: the same launches,
+        eagerly)."""
+        eng = self.engine
+        dev = eng.device
+        seq_d1 = torch.as_tensor(users["seq_d1"]).to(dev, torch.int64)
+        seq_d2 = torch.as_tensor(users["seq_d2"]).to(dev, torch.int64)
+        if seq_d1.dim() != 3 or seq_d1.shape != seq_d2.shape:
+            raise ValueError("encode_users: seq_d1 and seq_d2 must be [n, B, T] tensors of one shape")
+        n, B, T = seq_d1.shape
+        dom = torch.as_tensor(users["domain_id"]).to(dev, torch.int64).reshape(n, B)
+        self._check_comp_batch(B)
+        pl = eng.plan(B, T, 2, need_grad=False)              # recommend()'s plan
+        zero = torch.zeros(n, B, dtype=torch.int64, device=dev)
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        packed = eng.pack_epoch(pl, zero, zero.view(n, B, 1), seq_d1, seq_d2, torch.zeros(B, 2, device=dev), dom)
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        raw = eng.encode_epoch(pl, packed, use_graph=use_graph)
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(pl)
+        if raw.shape[1] == 1:
+            return raw[:, 0]
+        idx = (dom != 0).to(torch.int64).view(n, 1, B, 1).expand(n, 1, B, raw.shape[3])
+        return torch.gather(raw, 1, idx)[:, 0].contiguous()
+
+    @torch.no_grad()
+    def recommend_from_vectors(self, u, domain_id, k: int = 10, pool=None, history=None):
+        """The scorer alone: the k items the model scores highest for each stored user vector u [B, D] (encode_users' rows; any B -- the
+        vectors are already mixed), in the domain domain_id [B], best first, ties to the lower id.  pool / k as in recommend();
+        history [B, T] (optional): item ids to leave out of each row's list.  Returns (ids [B, k] int64, scores [B, k] float32) on the
+        device, padded with -1 / -inf."""
+        eng = self.engine
+        dev = eng.device
+        u = torch.as_tensor(u).to(dev, torch.float32).contiguous()
+        if u.dim() != 2 or u.shape[1] != eng.D or u.shape[0] < 1:
+            raise ValueError(f"recommend_from_vectors: u must be [B, {eng.D}] vectors")
+        B = u.shape[0]
+        dom = torch.as_tensor(domain_id).to(dev, torch.int64).reshape(B).contiguous()
+        if not 1 <= int(k) <= 256:
+            raise ValueError(f"k must be in 1..256, got {k}")
+        if history is not None:
+            history = torch.as_tensor(history).to(dev, torch.int64).contiguous()
+            if history.dim() != 2 or history.shape[0] != B:
+                raise ValueError("recommend_from_vectors: history must be [B, T] item ids")
+        if eng.table_m is not None:
+            eng.flush_table()
+        pools = self._candidate_pools(pool)
+        if min(int(q.numel()) for q in pools) < 1:
+            raise ValueError("recommend_from_vectors: an empty candidate pool")
+        ids = torch.empty(B, int(k), dtype=torch.int64, device=dev)
+        scores = torch.empty(B, int(k), dtype=torch.float32, device=dev)
+        flags = eng.flags_holder()
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        eng.enqueue_topk_vectors(u, dom, pools, history, int(k), ids, scores, flags.err)
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(flags)
+        return ids, scores
+
+    NEIGHBOR_CHUNK = 4096         # queries per launch of similar_items
+
+    @torch.no_grad()
+    def neighbors(self, queries, base=None, k: int = 10, metric: str = "cosine", pool=None, exclude_self: bool = True):
+        """Exact k nearest neighbours in an embedding space: queries -- int64 ids [Q] (rows of base) or float32 vectors [Q, D] -- against
+        the rows of base, by "cosine" or "dot", best first, ties to the lower id.  base=None: the item table (pending lazy-Adam rows are
+        flushed first); otherwise any contiguous float32 device tensor [N, D], D 64 / 128 -- stored encode_users output, say.  pool: the
+        candidate rows (None: every row).  exclude_self (id queries only; ignored for vectors) leaves a query's own row out of its list.
+        Returns (ids [Q, k] int64, scores [Q, k] float32) on the device, padded with -1 / -inf.  A score depends on its two rows only:
+        bit-identical rows tie exactly."""
+        eng = self.engine
+        dev = eng.device
+        if metric not in eng.NEIGHBOR_METRICS:
+            raise ValueError(f"metric must be one of {sorted(eng.NEIGHBOR_METRICS)}, got {metric!r}")
+        if not 1 <= int(k) <= 256:
+            raise ValueError(f"k must be in 1..256, got {k}")
+        if base is None:
+            if eng.table_m is not None:
+                eng.flush_table()
+            base = eng.table
+        if not (isinstance(base, torch.Tensor) and base.device == dev and base.dtype == torch.float32 and base.dim() == 2
+                and base.is_contiguous() and base.shape[0] >= 1):
+            raise ValueError("neighbors: base must be a contiguous float32 [N, D] tensor on the model's device")
+        if base.shape[1] not in (64, 128):
+            raise ValueError(f"neighbors: D must be 64 or 128, got {base.shape[1]}")
+        q = torch.as_tensor(queries)
+        if q.dtype.is_floating_point:
+            q = q.to(dev, torch.float32).contiguous()
+            if q.dim() != 2 or q.shape[1] != base.shape[1]:
+                raise ValueError(f"neighbors: vector queries must be [Q, {base.shape[1]}]")
+            exclude_self = False
+        else:
+            q = q.to(dev, torch.int64).reshape(-1).contiguous()
+        if q.shape[0] < 1:
+            raise ValueError("neighbors: no queries")
+        if pool is not None:
+            pool = self._candidate_pools(pool)[0]
+            if pool.numel() < 1:
+                raise ValueError("neighbors: an empty candidate pool")
+        ids = torch.empty(q.shape[0], int(k), dtype=torch.int64, device=dev)
+        scores = torch.empty(q.shape[0], int(k), dtype=torch.float32, device=dev)
+        flags = eng.flags_holder()
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        for c0 in range(0, q.shape[0], self.NEIGHBOR_CHUNK):      # chunked on the host: a whole pool can be the queries
+            c1 = min(q.shape[0], c0 + self.NEIGHBOR_CHUNK)
+            eng.enqueue_neighbors(q[c0:c1], base, pool, metric, int(k), bool(exclude_self), ids[c0:c1], scores[c0:c1], flags.err)
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(flags)
+        return ids, scores
+
+    def similar_items(self, ids, k: int = 10, metric: str = "cosine", pool=None):
+        """The k items nearest to each item of `ids` in the trained item table, the item itself left out: neighbors(ids, base=None,
+        exclude_self=True)."""
+        return self.neighbors(ids, base=None, k=k, metric=metric, pool=pool, exclude_self=True)
+
     def check_indices(self) -> None:
         """Raise IndexError if any batch since the last check carried an item id outside the table (nn.Embedding raises on the spot,
         model_seq.py:27-29; the fused step flags it on the device and keeps going with row 0).  One device -> host read: call it

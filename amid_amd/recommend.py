@@ -11,9 +11,18 @@ Takes the model flags of ``train_sr.py`` (``--model --emb_dim --hid_dim --seq_le
                             full: that item appended again -- the recommendation after the whole history
     --out FILE.npz          user_id [N], domain_id [N], items [N, K] (CSV item ids, -1 where a pool ran out), scores [N, K], in CSV row order
     --metrics               also evaluate these weights with test() on the same CSV (sampled negatives, drop_last), printed and returned
+    --vectors_out FILE.npz  also write the vector the scorer sees for every row of the CSV (SASRec.encode_users): user_id [N],
+                            domain_id [N], vectors [N, D] -- the encode half of an encode-nightly / score-online split
+    --similar_items {all | FILE}
+                            instead of recommendations, write to --out the --topk nearest neighbours (--metric cosine | dot) in the
+                            trained item table of every item of the candidate pools (all) or of the ids listed in FILE (text, or
+                            .npy): item_id [M], neighbors [M, K] (-1 where the candidates ran out), scores [M, K].  The candidates are
+                            --pool's: the union of the two dataset pools, or every row of the table
 
     python recommend.py --data_root /path/to/AMID -ds amazon -dm cloth_sport --overlap_ratio 0.75 --model sasrec --bs 256 \
         --seq_len 50 --emb_dim 128 --weights runs/seed0/best_d1.pt --topk 10 --out cloth_sport_top10.npz
+    python recommend.py ... --weights runs/seed0/best_d1.pt --vectors_out cloth_sport_users.npz
+    python recommend.py ... --weights runs/seed0/best_d1.pt --similar_items all --metric cosine --topk 20 --out cloth_sport_similar.npz
 
 Every row of the CSV gets a recommendation: the last batch is filled with rows from the start of the CSV (comp models need whole
 ``--bs``-row batches) and the surplus is cut off.  The ranking is ``SASRec.recommend_all``: one graph replay a batch.
@@ -42,6 +51,9 @@ def build_parser():
     p.add_argument("--history", type=str, default="eval", choices=("eval", "full"))
     p.add_argument("--out", type=str, default="recommendations.npz")
     p.add_argument("--metrics", action="store_true", help="also run test() on the CSV with these weights")
+    p.add_argument("--vectors_out", type=str, default=None, help="FILE.npz: also write user_id, domain_id and the scorer's vector of every row")
+    p.add_argument("--similar_items", type=str, default=None, help="all | FILE of item ids: write their --topk nearest items to --out instead")
+    p.add_argument("--metric", type=str, default="cosine", choices=("cosine", "dot"), help="the similarity of --similar_items")
     return p
 
 
@@ -59,6 +71,37 @@ def filled_batches(n_rows: int, bs: int) -> np.ndarray:
     """Row indices [n_batches, bs] covering 0 .. n_rows - 1 in order; the last batch's tail is rows from the start again."""
     nb = (n_rows + bs - 1) // bs
     return (np.arange(nb * bs) % n_rows).reshape(nb, bs)
+
+
+def listed_ids(path: str) -> np.ndarray:
+    """--similar_items FILE: the item ids of a .npy array or of a text file (whitespace or commas between them)."""
+    if path.endswith(".npy"):
+        return np.load(path).astype(np.int64).reshape(-1)
+    with open(path) as f:
+        return np.array([int(x) for x in f.read().replace(",", " ").split()], dtype=np.int64)
+
+
+def write_npz(path: str, out) -> None:
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.savez(path, **out)
+
+
+def similar_items_main(model, args, pool) -> dict:
+    """--similar_items: the neighbours of the pools' items (or the listed ones) among --pool's candidates, to --out."""
+    dev = torch.device(args.device)
+    cand = None if pool is None else torch.unique(torch.cat(pool))
+    if args.similar_items == "all":
+        items = cand if cand is not None else torch.arange(model.engine.n_rows, dtype=torch.int64, device=dev)
+    else:
+        items = torch.from_numpy(listed_ids(args.similar_items)).to(dev)
+        if items.numel() < 1:
+            raise SystemExit(f"{args.similar_items}: no item ids")
+    ids, scores = model.similar_items(items, k=args.topk, metric=args.metric, pool=cand)
+    out = {"item_id": items.cpu().numpy(), "neighbors": ids.cpu().numpy(), "scores": scores.cpu().numpy()}
+    write_npz(args.out, out)
+    print(f"wrote {args.out}: the {args.topk} nearest items ({args.metric}) of {items.numel()} items")
+    return out
 
 
 def load_weights(model, path: str) -> str:
@@ -107,14 +150,26 @@ def main(argv=None):
     sel = filled_batches(len(ds), args.bs)
     users = {"seq_d1": torch.from_numpy(s1[sel]).to(dev), "seq_d2": torch.from_numpy(s2[sel]).to(dev),
              "domain_id": torch.from_numpy(ds.domain_id[sel]).to(dev)}
-    ids, scores = model.recommend_all(users, k=args.topk, pool=pool, exclude_history=True, use_graph=not args.no_graph)
     N = len(ds)
+    vectors = None
+    if args.vectors_out:
+        vectors = model.encode_users(users, use_graph=not args.no_graph).reshape(-1, args.emb_dim)[:N].cpu().numpy()
+        write_npz(args.vectors_out, {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy(), "vectors": vectors})
+        print(f"wrote {args.vectors_out}: the scorer's vectors of {N} rows")
+    if args.similar_items:
+        out = similar_items_main(model, args, pool)
+        if vectors is not None:
+            out["vectors"] = vectors
+        return out
+    ids, scores = model.recommend_all(users, k=args.topk, pool=pool, exclude_history=True, use_graph=not args.no_graph)
     out = {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy(),
            "items": ids.reshape(-1, args.topk)[:N].cpu().numpy(), "scores": scores.reshape(-1, args.topk)[:N].cpu().numpy()}
     if os.path.dirname(args.out):
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
     np.savez(args.out, **out)
     print(f"wrote {args.out}: top-{args.topk} of {N} rows ({sel.shape[0]} batches of {args.bs})")
+    if vectors is not None:
+        out["vectors"] = vectors
     out["metrics"] = None
     if args.metrics:
         val = DeviceBatches(ds, args.bs, shuffle=False, device=args.device, seed=0)

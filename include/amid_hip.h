@@ -1133,6 +1133,29 @@ int amid_topk_users_f32(const float* u, long long u_dom_stride, const long long*
 int amid_own_from_seq_i64(const long long* seq_d1, const long long* seq_d2, const long long* domain_id, int B, int T, int* cnt,
                           long long* own, int* own_off, void* stream);
 
+/* ---- exact k-nearest neighbours of fp32 vectors (csrc/neighbors.hip) ---------------------------------------------------------------------------
+ * Q queries against the candidate rows of base [n_rows, D] (contiguous): the item table, or any stored matrix of vectors.  A query is a
+ * vector (queries [Q, D], query_ids null) or a row of base (query_ids [Q], queries null) -- exactly one of the two.  Candidates: the rows
+ * pool[0 .. n_pool) (sorted unique), or with pool null every row (n_pool is then ignored).  metric 0: the dot product; 1: the cosine
+ * a.b / (max(|a|, 1e-8) max(|b|, 1e-8)), every row's inverse norm formed once per call.  exclude_self (needs query_ids): candidate
+ * query_ids[q] is left out of query q's list.
+ * ids / scores [Q, k]: the k best candidates, best first, ties to the lower id; fewer than k candidates: id -1, score -inf (amid_topk_f32's
+ * contract).  A score is a function of its two rows only -- a fixed k-order chain on v_mfma_f32_16x16x4_f32 (bitwise an fmaf chain), the
+ * same bits in any tile, slot, workgroup or pool -- so bit-identical rows tie exactly.
+ * 1 <= k <= 256; D 64 / 128 (else AMID_ERR_UNSUPPORTED); null or inconsistent pointers, Q <= 0, n_rows <= 0 or >= 2^31 - 1, n_pool <= 0 with a
+ * pool, k out of range: AMID_ERR_ARG; both before any device call.  A query id or pool id outside [0, n_rows) raises AMID_FLAG_INDEX_RANGE in
+ * *flags and is never dereferenced: the candidate is absent, the query's row comes out as padding.  Row offsets are 64-bit.
+ * workspace: amid_neighbors_workspace_bytes(Q, n_cand, D, k) bytes, n_cand = n_pool or n_rows (negative: bad sizes; non-decreasing in Q,
+ * n_cand and k).  Launches on the stream only, no host read.
+ * amid_neighbors_target_workgroups(wgs): how many workgroups the scan aims at when it cuts the candidate tiles into ranges (default 256, one
+ * per CU; 1 .. 256, anything below 1 restores the default); returns the value before.  Process-wide and not a tuning knob: the tests use it
+ * to reach ranges of several tiles at small sizes (1: one range walks every tile).  The results do not depend on it. */
+long long amid_neighbors_workspace_bytes(int Q, long long n_cand, int D, int k);
+int amid_neighbors_target_workgroups(int wgs);
+int amid_neighbors_f32(const float* queries, const long long* query_ids, int Q, const float* base, long long n_rows, int D,
+                       const long long* pool, long long n_pool, int metric, int k, int exclude_self, void* workspace, int* flags,
+                       long long* ids, float* scores, void* stream);
+
 /* ---- BERT4Rec strips on bf16 pieces (round 5; csrc/bert_strip.hip MODE 3) ------------------------------------------------------------------
  * The strip launches of a TransformerBlock (model_seq.py:242-245 and its autograd) with every product as six bf16 piece pairs at fp32
  * accuracy -- what SASRec's strips run on since round 4.  Each 128 x 128 weight TILE a chain multiplies with is a three-plane fragment image
