@@ -10,61 +10,89 @@
 //     u_g[b]  = 0.5 mean_t f_g[b,t] + 0.5 c_g
 // Three small kernels: the pair-max per batch row (the only part that needs the full features), and a single-workgroup
 // mix forward / backward over [B, D] means.  Batch-coupled by construction (trans_bs is Linear(bs, 1) over the batch).
+// GRU4Rec uses the module the same way on its GRU outputs (model_seq.py:97-104): f = h, no LayerNorm -- the pair-max on raw rows
+// (amid_itc_pairmax_raw_f32: the same kernel body, in a whole-row and a blocked form), then the same mix kernels.
 #include "itc_mix_parts.h"
 
 namespace amid {
 
-// ---- s_j: one workgroup per batch row; LN_last of both domains' rows staged in LDS, then all T x T dot products ----
+// ---- s_j: one workgroup per batch row; both domains' rows staged in LDS, then all T x T dot products -------------------------
+// LN = true (SASRec, amid_itc_pairmax_f32): the rows pass through the domain's last LayerNorm on their way into LDS.  LN = false (GRU4Rec,
+// amid_itc_pairmax_raw_f32): no LayerNorm, rows enter LDS as read.  TB = rows of a domain staged at a time: TB >= T is the whole-row form
+// (one pass, both domains' T rows resident); TB < T is the blocked form -- a block of domain 0 is staged, the blocks of domain 1 pass
+// under it in turn, and the maximum and the two row sums are carried in registers across blocks.  Every dot product has the same fma
+// order in both forms and the row sums add their rows in the same order t = 0 .. T - 1, so the forms agree bit for bit.
 struct PairMaxArgs {
     const float* x;                       // [2, B, T, D] output of the last encoder layer
     const float* lnw[2]; const float* lnb[2];
     float* s;                             // [B]
     float* u_raw;                         // optional [2, B, D]: mean_t LN_last(x[g, b]) (what amid_lnmean_fwd_f32 computes)
     int B, T, D; float eps;
+    int TB;                               // rows of a domain per LDS block
 };
 
-__global__ __launch_bounds__(256) void itc_pairmax_kernel(const PairMaxArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+// rows [t0, t0 + n) of x[g, b] -> F [n][D + 4]: 8 rows at a time, 32 lanes per row (D <= 128)
+template <bool LN>
+__device__ __forceinline__ void pairmax_stage(const PairMaxArgs& a, int g, int b, int t0, int n, float* F) {
     const int T = a.T, D = a.D, LD = D + 4, q = D >> 2;
-    float* F[2] = {smem, smem + T * LD};
-    __shared__ float red[4];
-    const int b = blockIdx.x;
-    const int sub = threadIdx.x & 31, rg = threadIdx.x >> 5;          // 8 rows at a time, 32 lanes per row (D <= 128)
-    for (int g = 0; g < 2; ++g) {
-        const float* xb = a.x + ((long long)g * a.B + b) * T * D;
-        const bool on = sub < q;
+    const int sub = threadIdx.x & 31, rg = threadIdx.x >> 5;
+    const float* xb = a.x + (((long long)g * a.B + b) * T + t0) * D;
+    const bool on = sub < q;
+    if (LN) {
         float4 ww = make_float4(1.f, 1.f, 1.f, 1.f), bb = make_float4(0.f, 0.f, 0.f, 0.f);
         if (on) { ww = ld4(a.lnw[g] + 4 * sub); bb = ld4(a.lnb[g] + 4 * sub); }
-        for (int t = rg; t < T; t += 8) {
+        for (int t = rg; t < n; t += 8) {
             float4 y = on ? ld4(xb + (long long)t * D + 4 * sub) : make_float4(0.f, 0.f, 0.f, 0.f);
             const float mean = group_sum<32>(f4hsum(y)) / D;
             float4 d4 = make_float4(y.x - mean, y.y - mean, y.z - mean, y.w - mean);
             if (!on) d4 = make_float4(0.f, 0.f, 0.f, 0.f);
             const float rstd = 1.0f / sqrtf(group_sum<32>(f4hsum(f4mul(d4, d4))) / D + a.eps);
-            if (on) st4(F[g] + t * LD + 4 * sub, make_float4(d4.x * rstd * ww.x + bb.x, d4.y * rstd * ww.y + bb.y,
-                                                             d4.z * rstd * ww.z + bb.z, d4.w * rstd * ww.w + bb.w));
+            if (on) st4(F + t * LD + 4 * sub, make_float4(d4.x * rstd * ww.x + bb.x, d4.y * rstd * ww.y + bb.y,
+                                                          d4.z * rstd * ww.z + bb.z, d4.w * rstd * ww.w + bb.w));
+        }
+    } else {
+        for (int t = rg; t < n; t += 8)
+            if (on) st4(F + t * LD + 4 * sub, ld4(xb + (long long)t * D + 4 * sub));
+    }
+}
+
+template <bool LN>
+__global__ __launch_bounds__(256) void itc_pairmax_kernel(const PairMaxArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int T = a.T, D = a.D, LD = D + 4, q = D >> 2, TB = min(a.TB, T);
+    float* F[2] = {smem, smem + TB * LD};
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const int ug = (int)threadIdx.x / D, ud = (int)threadIdx.x - ug * D;     // 2 D <= 256: thread (g, d) carries column d of domain g's row sum
+    const bool usum = a.u_raw != nullptr && (int)threadIdx.x < 2 * D;
+    float uacc = 0.f, best = -INFINITY;
+    for (int i0 = 0; i0 < T; i0 += TB) {
+        const int n0 = min(TB, T - i0);
+        pairmax_stage<LN>(a, 0, b, i0, n0, F[0]);
+        for (int j0 = 0; j0 < T; j0 += TB) {
+            const int n1 = min(TB, T - j0);
+            pairmax_stage<LN>(a, 1, b, j0, n1, F[1]);
+            __syncthreads();
+            if (usum && (ug == 0 ? j0 == 0 : i0 == 0)) {                      // every block of a domain is summed once, in the order of t
+                const float* f = F[ug] + ud;
+                const int n = ug == 0 ? n0 : n1;
+                for (int t = 0; t < n; ++t) uacc += f[t * LD];
+            }
+            for (int p = threadIdx.x; p < n0 * n1; p += 256) {
+                const int i = p / n1, j = p - i * n1;
+                const float* fa = F[0] + i * LD;
+                const float* fc = F[1] + j * LD;
+                float acc = 0.f;
+                for (int c = 0; c < q; ++c) {
+                    const float4 u = ld4(fa + 4 * c), v = ld4(fc + 4 * c);
+                    acc = fmaf(u.x, v.x, acc); acc = fmaf(u.y, v.y, acc); acc = fmaf(u.z, v.z, acc); acc = fmaf(u.w, v.w, acc);
+                }
+                best = fmaxf(best, acc);
+            }
+            if (TB < T) __syncthreads();                                      // blocked form: the next block overwrites what was just read
         }
     }
-    __syncthreads();
-    if (a.u_raw != nullptr)
-        for (int e = threadIdx.x; e < 2 * D; e += 256) {
-            const int g = e / D, d = e - g * D;
-            float acc = 0.f;
-            for (int t = 0; t < T; ++t) acc += F[g][t * LD + d];
-            a.u_raw[((long long)g * a.B + b) * D + d] = acc / T;
-        }
-    float best = -INFINITY;
-    for (int p = threadIdx.x; p < T * T; p += 256) {
-        const int i = p / T, j = p - i * T;
-        const float* fa = F[0] + i * LD;
-        const float* fc = F[1] + j * LD;
-        float acc = 0.f;
-        for (int c = 0; c < q; ++c) {
-            const float4 u = ld4(fa + 4 * c), v = ld4(fc + 4 * c);
-            acc = fmaf(u.x, v.x, acc); acc = fmaf(u.y, v.y, acc); acc = fmaf(u.z, v.z, acc); acc = fmaf(u.w, v.w, acc);
-        }
-        best = fmaxf(best, acc);
-    }
+    if (usum) a.u_raw[((long long)ug * a.B + b) * D + ud] = uacc / T;
     best = group_max<64>(best);
     if (lane_id() == 0) red[wave_id()] = best;
     __syncthreads();
@@ -486,21 +514,43 @@ __global__ __launch_bounds__(512) void itc_mix_bwd_fast_kernel(const MixArgs a) 
 
 using namespace amid;
 
+// LDS of the whole-row form; above it the LayerNorm form refuses and the raw form runs blocked
+static const size_t PAIRMAX_LDS_MAX = 160 * 1024 - 256;
+static const int PAIRMAX_TB = 64;                                  // blocked form: 2 x 64 rows = 66 KiB at D = 128 (two workgroups per CU)
+
+template <bool LN>
+static int pairmax_launch(PairMaxArgs& a, size_t lds, void* stream) {
+    hipError_t e = hipFuncSetAttribute((const void*)itc_pairmax_kernel<LN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    itc_pairmax_kernel<LN><<<a.B, 256, lds, (hipStream_t)stream>>>(a);
+    AMID_LAUNCH_CHECK();
+    return AMID_OK;
+}
+
 // Pointer-array parameters are HOST arrays of 2 device pointers (itc_d1, itc_d2 / sac1, sac2).
 extern "C" int amid_itc_pairmax_f32(const float* x, const float* const* ln_w, const float* const* ln_b, int B, int T, int D, float eps,
                                     float* s, float* u_raw, void* stream) {
     AMID_CHECK_ARG(x && ln_w && ln_b && ln_w[0] && ln_w[1] && ln_b[0] && ln_b[1] && s && B > 0 && T > 0 && D > 0 && (D % 4) == 0);
     if (D > 128) return AMID_ERR_UNSUPPORTED;
     const size_t lds = (size_t)2 * T * (D + 4) * sizeof(float);
-    if (lds > 160 * 1024 - 256) return AMID_ERR_UNSUPPORTED;       // T <= 154 at D = 128 (both domains' LayerNorm'd rows of a batch row)
+    if (lds > PAIRMAX_LDS_MAX) return AMID_ERR_UNSUPPORTED;       // T <= 154 at D = 128 (both domains' LayerNorm'd rows of a batch row)
     PairMaxArgs a;
-    a.x = x; a.s = s; a.u_raw = u_raw; a.B = B; a.T = T; a.D = D; a.eps = eps;
+    a.x = x; a.s = s; a.u_raw = u_raw; a.B = B; a.T = T; a.D = D; a.eps = eps; a.TB = T;
     for (int g = 0; g < 2; ++g) { a.lnw[g] = ln_w[g]; a.lnb[g] = ln_b[g]; }
-    hipError_t e = hipFuncSetAttribute((const void*)itc_pairmax_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    itc_pairmax_kernel<<<B, 256, lds, (hipStream_t)stream>>>(a);
-    AMID_LAUNCH_CHECK();
-    return AMID_OK;
+    return pairmax_launch<true>(a, lds, stream);
+}
+
+// The pair-max on raw rows (GRU4Rec: no last LayerNorm).  Whole-row form while both domains' rows fit (2 T (D + 4) floats <= 160 KiB - 256
+// bytes: T <= 154 at D = 128), the blocked form (64 rows of each domain at a time) above: any T.
+extern "C" int amid_itc_pairmax_raw_f32(const float* x, int B, int T, int D, float* s, float* u_raw, void* stream) {
+    AMID_CHECK_ARG(x && s && B > 0 && T > 0 && D > 0 && (D % 4) == 0);
+    if (D > 128) return AMID_ERR_UNSUPPORTED;
+    PairMaxArgs a = {};
+    a.x = x; a.s = s; a.u_raw = u_raw; a.B = B; a.T = T; a.D = D; a.eps = 0.f;
+    size_t lds = (size_t)2 * T * (D + 4) * sizeof(float);
+    a.TB = T;
+    if (lds > PAIRMAX_LDS_MAX) { a.TB = PAIRMAX_TB; lds = (size_t)2 * PAIRMAX_TB * (D + 4) * sizeof(float); }
+    return pairmax_launch<false>(a, lds, stream);
 }
 
 static int mix_fill(MixArgs& a, const float* u_raw, const float* const* w_nn, const float* const* b_nn, const float* const* w_bs,

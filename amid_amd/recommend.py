@@ -36,7 +36,7 @@ import torch
 
 from . import train_sr as base
 from .dataset_seq import DeviceBatches, DualDomainSeqDataset
-from .model_gru import GRU4Rec
+from .model_gru import GRU4Rec, GRU4RecAMID
 from .model_seq import BERT4Rec, SASRec
 
 
@@ -123,6 +123,8 @@ def main(argv=None):
     cls = {"gru4rec": GRU4Rec, "sasrec": SASRec, "bert4rec": BERT4Rec}.get(args.model.lower())
     if cls is None:
         raise SystemExit(f"unknown --model {args.model!r} (gru4rec | sasrec | bert4rec)")
+    if cls is GRU4Rec and (args.isInC or args.isItC or args.isDR):
+        cls = GRU4RecAMID                                                                  # (the plain class refuses the flags: model_gru.py)
     user_length, item_length = 895510, 447410                                             # train_sr.py:447, :450
     root = os.path.join(args.data_root, f"{args.dataset_type}_dataset")
     users_csv = args.users or os.path.join(root, f"{args.domain_type}_test.csv")

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .dataset_seq import DeviceBatches, DualDomainSeqDataset, JointBatches
-from .model_gru import GRU4Rec
+from .model_gru import GRU4Rec, GRU4RecAMID
 from .model_seq import BERT4Rec, SASRec
 from .utils import AverageMeter, device_positive_ranks, init_logger, scores_from_ranks
 
@@ -407,6 +407,8 @@ def main(argv=None):
             raise SystemExit(f"unknown --model {args.model!r} (gru4rec | sasrec | bert4rec)")
         if cls is GRU4Rec and world > 1:
             raise SystemExit("--model gru4rec trains on one GPU: its data-parallel step is not built")
+        if cls is GRU4Rec and (args.isInC or args.isItC):
+            cls = GRU4RecAMID                                                              # (the plain class refuses the flags: model_gru.py)
         torch.cuda.set_device(torch.device(args.device))
         model = cls(user_length=user_length, user_emb_dim=args.emb_dim, item_length=item_length, item_emb_dim=args.emb_dim,
                     seq_len=args.seq_len, hid_dim=args.hid_dim, bs=args.bs * (world if (args.isItC or args.isInC) else 1), isInC=args.isInC, isItC=args.isItC,

@@ -26,6 +26,7 @@ import torch
 
 from . import train_sr as base
 from .dataset_seq import DeviceBatches, DualDomainSeqDataset
+from .model_gru import GRU4RecAMID
 from .model_seq import BERT4Rec, SASRec
 from .utils import AverageMeter, init_logger
 
@@ -129,8 +130,9 @@ def main(argv=None):
     if not args.isDR:
         raise SystemExit("train_sr_dr.py trains the doubly-robust heads (the reference's loop unpacks six outputs, train_sr_dr.py:204); "
                          "use train_sr.py without them")
-    if args.model.lower() not in ("sasrec", "bert4rec"):
-        raise SystemExit("the doubly-robust heads are built for --model sasrec (what run.sh trains) and bert4rec")
+    classes = {"sasrec": SASRec, "bert4rec": BERT4Rec, "gru4rec": GRU4RecAMID}
+    if args.model.lower() not in classes:
+        raise SystemExit(f"unknown --model {args.model!r} (gru4rec | sasrec | bert4rec)")
     # one process per GPU under `python -m torch.distributed.run --nproc-per-node N train_sr_dr.py ...` (the reference is single-GPU):
     # --bs is the batch PER GPU, both loops shard their batches by rank and exchange gradients every step (amid_amd/dist.py); with
     # --isItC (run.sh) InterComp's Linear(bs, 1) spans the GLOBAL batch of world x --bs rows (engine._enqueue_user_vectors)
@@ -154,7 +156,7 @@ def main(argv=None):
         train_batches_dr = DeviceBatches(ds_dr, args.bs, shuffle=True, device=args.device, seed=500 + i, rank=rank, world=world)
         val_batches = DeviceBatches(ds_val, gbs, shuffle=False, device=args.device, seed=i)
         torch.cuda.set_device(torch.device(args.device))
-        model = (SASRec if args.model.lower() == "sasrec" else BERT4Rec)(user_length=2 * user_length, user_emb_dim=args.emb_dim, item_length=2 * item_length, item_emb_dim=args.emb_dim,
+        model = classes[args.model.lower()](user_length=2 * user_length, user_emb_dim=args.emb_dim, item_length=2 * item_length, item_emb_dim=args.emb_dim,
                        seq_len=args.seq_len, hid_dim=args.hid_dim, bs=gbs, isInC=args.isInC, isItC=args.isItC, threshold1=args.ts1,
                        threshold2=args.ts2, isDR=True, lr=args.lr, seed=i, **({"compute": "bf16"} if args.dtype == "bf16" else {}))
         model.engine.dr_e_w = float(args.dr_e_w)

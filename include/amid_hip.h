@@ -414,6 +414,15 @@ int amid_sample_negatives_i64(const long long* pool_d1, int n_pool_d1, const lon
 int amid_itc_pairmax_f32(const float* x, const float* const* ln_w, const float* const* ln_b, int B, int T, int D, float eps, float* s,
                          float* u_raw /* optional [2, B, D]: also emit mean_t LN_last(x), saving the amid_lnmean_fwd_f32 launch */,
                          void* stream);
+/* The pair-max on RAW rows, for a backbone without a last LayerNorm (GRU4Rec, model_seq.py:97-101: InterComp on the GRU outputs):
+ *   s[j] = max_{a,c} x[0,j,a] . x[1,j,c],   u_raw[g][j] = mean_t x[g,j,t]   (optional; what amid_lnmean_fwd_f32 gives with null LayerNorm)
+ * x [2, B, T, D].  One workgroup per batch row, the same kernel body as amid_itc_pairmax_f32 without the LayerNorm.  Two forms:
+ *   whole-row : 2 T (D + 4) floats <= 160 KiB - 256 bytes (T <= 154 at D = 128) -- both domains' rows of a batch row resident in LDS;
+ *   blocked   : above that, for any T -- 64 rows of domain 0 staged, the 64-row blocks of domain 1 pass under them in turn; the maximum
+ *               and the two row sums are carried across blocks.
+ * Every dot product has one fma order and the row sums add t = 0 .. T - 1 in order in both forms, so a row's s and u_raw do not depend on
+ * the form.  AMID_ERR_ARG: null x or s, B, T or D <= 0, D % 4 != 0; AMID_ERR_UNSUPPORTED: D > 128 -- all before anything touches a device. */
+int amid_itc_pairmax_raw_f32(const float* x, int B, int T, int D, float* s, float* u_raw /* optional [2, B, D] */, void* stream);
 int amid_itc_mix_fwd_f32(const float* u_raw, const float* s, const float* const* w_nn, const float* const* b_nn,
                          const float* const* w_bs, const float* const* b_bs, float threshold, int B, int D, float* gate, float* z,
                          float* sw, float* u_mix, void* stream);
