@@ -1,5 +1,5 @@
 // The running best-K list of the top-K kernels (full_rank.hip: users against their pools through predictModule; neighbors.hip: exact nearest
-// neighbours of fp32 vectors): a list per query in LDS, and the merge of a tile's newcomers into it by a bitonic sort of (list + newcomers).
+// neighbours of fp32 vectors; audience.hip: stored user vectors against an item): a list per query in LDS, and the merge of a tile's newcomers into it by a bitonic sort of (list + newcomers).
 // Order: larger score first, ties to the lower id.  Every workgroup that uses it has FR_THREADS threads.
 #pragma once
 #include "common.h"
@@ -15,28 +15,13 @@ __device__ __forceinline__ bool fr_before(float s1, int i1, float s2, int i2) { 
 struct FrList { float* s; int* id; int* n; };          // one running best-K list in LDS
 struct FrScratch { float* s; int* id; int* wcnt; };    // merge buffer [512] scores, [512] ids; per-wave counts [4]
 
-// Offer one candidate per thread (cand: it takes part) to the list; every thread of the workgroup calls this.  Newcomers that beat the
-// list's K-th entry (or join a list not yet full) go behind the list in the merge buffer, list + newcomers are sorted (bitonic over the
-// next power of two, at most 512 entries) and the first K stay.
-__device__ __forceinline__ void fr_offer(const FrList& L, const FrScratch& S, int K, bool cand, float s, int id) {
-    const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
-    const int n = *L.n;
-    bool beat = cand;
-    if (cand && n == K) beat = fr_before(s, id, L.s[K - 1], L.id[K - 1]);
-    const unsigned long long m = __ballot(beat);
-    if (lane == 0) S.wcnt[w] = __popcll(m);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int v = 0; v < FR_THREADS / 64; ++v) { off += v < w ? S.wcnt[v] : 0; tot += S.wcnt[v]; }
-    __syncthreads();                                           // (every wave has read the counts before the next call writes them)
-    if (tot == 0) return;                                      // (uniform)
-    const int total = n + tot;
+// The merge step: the list's n entries go to the front of the merge buffer, whose entries [n, total) the caller has written (newcomers; no
+// barrier needed in between), the rest up to the next power of two is padded with empty slots, the buffer is sorted best first (bitonic, at
+// most 512 entries) and the first min(K, total) entries become the list.  Every thread of the workgroup calls this; it ends in a barrier.
+__device__ __forceinline__ void fr_sort_keep(const FrList& L, const FrScratch& S, int K, int n, int total) {
+    const int tid = threadIdx.x;
     int size = 2;
     while (size < total) size <<= 1;
-    if (beat) {
-        const int slot = n + off + __popcll(m & ((1ull << lane) - 1ull));
-        S.s[slot] = s; S.id[slot] = id;
-    }
     for (int i = tid; i < size; i += FR_THREADS) {
         if (i < n) { S.s[i] = L.s[i]; S.id[i] = L.id[i]; }
         else if (i >= total) { S.s[i] = -INFINITY; S.id[i] = FR_ID_NONE; }
@@ -60,6 +45,28 @@ __device__ __forceinline__ void fr_offer(const FrList& L, const FrScratch& S, in
     for (int i = tid; i < keep; i += FR_THREADS) { L.s[i] = S.s[i]; L.id[i] = S.id[i]; }
     if (tid == 0) *L.n = keep;
     __syncthreads();
+}
+
+// Offer one candidate per thread (cand: it takes part) to the list; every thread of the workgroup calls this.  Newcomers that beat the
+// list's K-th entry (or join a list not yet full) go behind the list in the merge buffer, list + newcomers are sorted (fr_sort_keep) and
+// the first K stay.
+__device__ __forceinline__ void fr_offer(const FrList& L, const FrScratch& S, int K, bool cand, float s, int id) {
+    const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+    const int n = *L.n;
+    bool beat = cand;
+    if (cand && n == K) beat = fr_before(s, id, L.s[K - 1], L.id[K - 1]);
+    const unsigned long long m = __ballot(beat);
+    if (lane == 0) S.wcnt[w] = __popcll(m);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int v = 0; v < FR_THREADS / 64; ++v) { off += v < w ? S.wcnt[v] : 0; tot += S.wcnt[v]; }
+    __syncthreads();                                           // (every wave has read the counts before the next call writes them)
+    if (tot == 0) return;                                      // (uniform)
+    if (beat) {
+        const int slot = n + off + __popcll(m & ((1ull << lane) - 1ull));
+        S.s[slot] = s; S.id[slot] = id;
+    }
+    fr_sort_keep(L, S, K, n, n + tot);
 }
 
 // LDS of fr_merge_ranges: list [K] scores | [K] ids | n [4] | merge [512] scores | [512] ids | wcnt [4]

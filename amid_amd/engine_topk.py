@@ -131,3 +131,54 @@ class TopkMixin:
                 ids[i].copy_(b_ids, non_blocking=True)
                 scores[i].copy_(b_scores, non_blocking=True)
         return ids, scores
+
+    # ------------------------------------------------------------------ audience top-K: the users of an item (csrc/audience.hip)
+    AUDIENCE_CHUNK = 1024         # query items per amid_audience_topk_f32 call at most (the workspace is sized for it)
+
+    def _audience_workspace(self, Q: int, n1: int, n2: int, k: int) -> torch.Tensor:
+        nbytes = int(lib().value("amid_audience_workspace_bytes", Q, n1, n2, self.hid, k))
+        if nbytes < 0:
+            raise ValueError(f"audience top-K: bad sizes Q {Q}, rows {n1} / {n2}, k {k}")
+        ws = getattr(self, "_au_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            if ws is not None:
+                ws.record_stream(self.stream)          # (launches still queued on the engine's stream may read the old one)
+            with torch.cuda.stream(self.stream):
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._au_ws = ws
+        return ws
+
+    def enqueue_audience_halves(self, vectors: torch.Tensor, slots) -> None:
+        """The user halves W1[:, :D] v + b1 of the listed rows of vectors [N, D] (contiguous float32 on the device) into the audience
+        workspace, for the weights as they are now: one launch (amid_audience_halves_f32).  slots = (domain 0's rows, domain 1's rows):
+        ascending int32 device tensors, not both empty.  The workspace is grown here to what any later enqueue_audience_topk on these
+        lists needs (AUDIENCE_CHUNK queries, k = 256), so it does not move between the two.  Nothing is synchronised."""
+        s1, s2 = slots
+        ws = self._audience_workspace(self.AUDIENCE_CHUNK, s1.numel(), s2.numel(), 256)
+        flags = self.flags_holder()
+        sc = self._scorer()
+        lib().call("amid_audience_halves_f32", vectors.data_ptr(), vectors.shape[0], s1.data_ptr() if s1.numel() else None, s1.numel(),
+                   s2.data_ptr() if s2.numel() else None, s2.numel(), sc["w1"], sc["b1"], self.D, self.hid, ws.data_ptr(), flags.err.data_ptr(),
+                   self.s)
+        self._au_halves = (ws.data_ptr(), s1.data_ptr(), s1.numel(), s2.data_ptr(), s2.numel())
+
+    def enqueue_audience_topk(self, items: torch.Tensor, item_domain: torch.Tensor, slots, holders, k: int, rows: torch.Tensor,
+                              scores: torch.Tensor, err: torch.Tensor) -> None:
+        """amid_audience_topk_f32 on the engine's stream: for each query item (items, item_domain [Q] int64, Q <= AUDIENCE_CHUNK) the k
+        best rows of its domain's list among those enqueue_audience_halves prepared for these `slots`, minus holders -- None, or
+        (indices int32 ascending within a query, offsets [Q + 1] int64 into indices); rows [Q, k] int64, scores [Q, k], err [1] int32
+        flags.  Nothing is synchronised."""
+        s1, s2 = slots
+        Q = items.shape[0]
+        if Q > self.AUDIENCE_CHUNK:
+            raise ValueError(f"enqueue_audience_topk: at most {self.AUDIENCE_CHUNK} queries a call, got {Q}")
+        ws = self._audience_workspace(Q, s1.numel(), s2.numel(), int(k))
+        if getattr(self, "_au_halves", None) != (ws.data_ptr(), s1.data_ptr(), s1.numel(), s2.data_ptr(), s2.numel()):
+            raise ValueError("enqueue_audience_topk: the workspace holds no user halves for these slot lists (enqueue_audience_halves)")
+        sc = self._scorer()
+        hold, hold_off = (None, None) if holders is None else (holders[0].data_ptr() if holders[0].numel() else None, holders[1].data_ptr())
+        if holders is not None and hold is None:
+            hold_off = None                               # (every list is empty)
+        lib().call("amid_audience_topk_f32", items.data_ptr(), item_domain.data_ptr(), Q, self.table.data_ptr(), self.n_rows, sc["w1"],
+                   sc["w2"], sc["b2"], s1.data_ptr() if s1.numel() else None, s1.numel(), s2.data_ptr() if s2.numel() else None, s2.numel(),
+                   hold, hold_off, self.D, self.hid, int(k), ws.data_ptr(), err.data_ptr(), rows.data_ptr(), scores.data_ptr(), self.s)

@@ -610,6 +610,68 @@ class SASRec(nn.Module):
         exclude_self=True)."""
         return self.neighbors(ids, base=None, k=k, metric=metric, pool=pool, exclude_self=True)
 
+    @torch.no_grad()
+    def recommend_users(self, items, item_domain, vectors, vector_domain, k: int = 10, holders=None):
+        """The audience of each item: the k rows of vectors [N, D] (stored encode_users output: contiguous float32 on the model's device,
+        already mixed for an isItC model) that predictModule scores highest for table row items[q], among the rows whose
+        vector_domain [N] equals item_domain[q], best first, ties to the lower row.  holders = (indices, offsets [Q + 1]): rows to leave
+        out of each query's audience, indices[offsets[q] : offsets[q + 1]] for query q -- in any order, duplicates allowed; entries of the
+        other domain or outside 0 .. N - 1 are ignored.  Returns (rows [Q, k] int64, scores [Q, k] float32) on the device, padded with
+        -1 / -inf where fewer than k candidates exist.  A score equals recommend_from_vectors' for the same vector and item bit for bit.
+        The user halves are formed once per call (SasrecEngine.enqueue_audience_halves); the queries go in chunks of
+        engine.AUDIENCE_CHUNK."""
+        eng = self.engine
+        dev = eng.device
+        if not (isinstance(vectors, torch.Tensor) and vectors.device == dev and vectors.dtype == torch.float32 and vectors.dim() == 2
+                and vectors.is_contiguous() and vectors.shape[0] >= 1 and vectors.shape[1] == eng.D):
+            raise ValueError(f"recommend_users: vectors must be a contiguous float32 [N, {eng.D}] tensor on the model's device")
+        N = vectors.shape[0]
+        if N >= 2 ** 31 - 1:
+            raise ValueError(f"recommend_users: at most 2^31 - 2 vectors, got {N}")
+        vdom = torch.as_tensor(vector_domain).to(dev, torch.int64).reshape(-1)
+        if vdom.numel() != N:
+            raise ValueError(f"recommend_users: vector_domain must have one entry per vector ({N}), got {vdom.numel()}")
+        q = torch.as_tensor(items).to(dev, torch.int64).reshape(-1).contiguous()
+        Q = q.shape[0]
+        if Q < 1:
+            raise ValueError("recommend_users: no query items")
+        qdom = torch.as_tensor(item_domain).to(dev, torch.int64).reshape(-1).contiguous()
+        if qdom.numel() != Q:
+            raise ValueError(f"recommend_users: item_domain must have one entry per item ({Q}), got {qdom.numel()}")
+        if not 1 <= int(k) <= 256:
+            raise ValueError(f"k must be in 1..256, got {k}")
+        hold = None
+        if holders is not None:
+            if not (isinstance(holders, (tuple, list)) and len(holders) == 2):
+                raise ValueError("recommend_users: holders is None or a pair (indices, offsets [Q + 1])")
+            h_idx = torch.as_tensor(holders[0]).to(dev, torch.int64).reshape(-1)
+            h_off = torch.as_tensor(holders[1]).to(dev, torch.int64).reshape(-1).contiguous()
+            if h_off.numel() != Q + 1:
+                raise ValueError(f"recommend_users: holders' offsets must have Q + 1 = {Q + 1} entries, got {h_off.numel()}")
+            if int(h_off[0]) != 0 or int(h_off[-1]) != h_idx.numel() or bool((h_off[1:] < h_off[:-1]).any()):
+                raise ValueError("recommend_users: holders' offsets must rise from 0 to the number of indices")
+            # ascending within each query's list: one sort of (query, row); rows outside 0 .. N - 1 become N, which no list holds
+            seg = torch.repeat_interleave(torch.arange(Q, device=dev), h_off[1:] - h_off[:-1])
+            idx = torch.where((h_idx < 0) | (h_idx >= N), torch.full_like(h_idx, N), h_idx)
+            key = torch.sort(seg * (N + 1) + idx).values
+            hold = ((key % (N + 1)).to(torch.int32).contiguous(), h_off)
+        if eng.table_m is not None:
+            eng.flush_table()
+        isd1 = vdom != 0
+        slots = (torch.nonzero(~isd1).reshape(-1).to(torch.int32).contiguous(), torch.nonzero(isd1).reshape(-1).to(torch.int32).contiguous())
+        rows = torch.empty(Q, int(k), dtype=torch.int64, device=dev)
+        scores = torch.empty(Q, int(k), dtype=torch.float32, device=dev)
+        flags = eng.flags_holder()
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        eng.enqueue_audience_halves(vectors, slots)
+        for c0 in range(0, Q, eng.AUDIENCE_CHUNK):               # chunked on the host: a whole catalog can be the queries
+            c1 = min(Q, c0 + eng.AUDIENCE_CHUNK)
+            eng.enqueue_audience_topk(q[c0:c1], qdom[c0:c1], slots, None if hold is None else (hold[0], hold[1][c0:c1 + 1]), int(k),
+                                      rows[c0:c1], scores[c0:c1], flags.err)
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(flags)
+        return rows, scores
+
     def check_indices(self) -> None:
         """Raise IndexError if any batch since the last check carried an item id outside the table (nn.Embedding raises on the spot,
         model_seq.py:27-29; the fused step flags it on the device and keeps going with row 0).  One device -> host read: call it

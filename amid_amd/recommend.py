@@ -18,11 +18,22 @@ Takes the model flags of ``train_sr.py`` (``--model --emb_dim --hid_dim --seq_le
                             trained item table of every item of the candidate pools (all) or of the ids listed in FILE (text, or
                             .npy): item_id [M], neighbors [M, K] (-1 where the candidates ran out), scores [M, K].  The candidates are
                             --pool's: the union of the two dataset pools, or every row of the table
+    --audience_of {all | FILE}
+                            instead of recommendations, write to --out the audience of items (SASRec.recommend_users): the --topk rows of
+                            --users that score the item highest, among the rows of the item's domain.  all: every item of the two
+                            dataset pools (--pool dataset), each in its pool's domain; FILE: "item_id domain_id" pairs (text, or a .npy
+                            array [M, 2]).  Written: item_id [M], domain_id [M], users [M, K] (the rows' user_id, -1 where the domain ran
+                            out of rows), rows [M, K] (CSV row numbers), scores [M, K]
+    --vectors_in FILE.npz   with --audience_of: take the rows' vectors from a file --vectors_out wrote for the same CSV instead of
+                            encoding them in this run
+    --exclude_holders       with --audience_of: leave out of an item's audience every row whose own-domain history, the held-out item
+                            included, contains the item
 
     python recommend.py --data_root /path/to/AMID -ds amazon -dm cloth_sport --overlap_ratio 0.75 --model sasrec --bs 256 \
         --seq_len 50 --emb_dim 128 --weights runs/seed0/best_d1.pt --topk 10 --out cloth_sport_top10.npz
     python recommend.py ... --weights runs/seed0/best_d1.pt --vectors_out cloth_sport_users.npz
     python recommend.py ... --weights runs/seed0/best_d1.pt --similar_items all --metric cosine --topk 20 --out cloth_sport_similar.npz
+    python recommend.py ... --weights runs/seed0/best_d1.pt --audience_of all --exclude_holders --topk 100 --out cloth_sport_audiences.npz
 
 Every row of the CSV gets a recommendation: the last batch is filled with rows from the start of the CSV (comp models need whole
 ``--bs``-row batches) and the surplus is cut off.  The ranking is ``SASRec.recommend_all``: one graph replay a batch.
@@ -54,6 +65,9 @@ def build_parser():
     p.add_argument("--vectors_out", type=str, default=None, help="FILE.npz: also write user_id, domain_id and the scorer's vector of every row")
     p.add_argument("--similar_items", type=str, default=None, help="all | FILE of item ids: write their --topk nearest items to --out instead")
     p.add_argument("--metric", type=str, default="cosine", choices=("cosine", "dot"), help="the similarity of --similar_items")
+    p.add_argument("--audience_of", type=str, default=None, help="all | FILE of 'item_id domain_id' pairs: write their --topk users to --out instead")
+    p.add_argument("--vectors_in", type=str, default=None, help="FILE.npz that --vectors_out wrote for --users: the vectors --audience_of ranks")
+    p.add_argument("--exclude_holders", action="store_true", help="--audience_of: leave out the rows whose history holds the item")
     return p
 
 
@@ -104,6 +118,77 @@ def similar_items_main(model, args, pool) -> dict:
     return out
 
 
+def listed_items(path: str):
+    """--audience_of FILE: (item ids, domain ids) of a .npy array [M, 2] or of a text file of "item_id domain_id" pairs (whitespace or
+    commas between the numbers)."""
+    if path.endswith(".npy"):
+        flat = np.load(path).astype(np.int64).reshape(-1)
+    else:
+        flat = listed_ids(path)
+    if flat.size < 2 or flat.size % 2:
+        raise SystemExit(f"{path}: expected 'item_id domain_id' pairs")
+    pairs = flat.reshape(-1, 2)
+    if not np.isin(pairs[:, 1], (0, 1)).all():
+        raise SystemExit(f"{path}: a domain_id is 0 or 1")
+    return pairs[:, 0].copy(), pairs[:, 1].copy()
+
+
+def holders_of(items: np.ndarray, item_dom: np.ndarray, seq_d1: np.ndarray, seq_d2: np.ndarray, i_node: np.ndarray, domain_id: np.ndarray):
+    """--exclude_holders: for each query (item, domain) the rows of that domain whose own-domain sequence or held-out item is the item,
+    as recommend_users' (indices, offsets [M + 1]) -- ascending rows, a row once per occurrence."""
+    d = (domain_id != 0).astype(np.int64)
+    own = np.concatenate((np.where(d[:, None] != 0, seq_d2, seq_d1), i_node[:, None]), axis=1).astype(np.int64)
+    key = (own * 2 + d[:, None]).reshape(-1)
+    rows = np.repeat(np.arange(own.shape[0], dtype=np.int64), own.shape[1])
+    order = np.argsort(key, kind="stable")
+    key, rows = key[order], rows[order]
+    qk = items.astype(np.int64) * 2 + (item_dom != 0)
+    lo, hi = np.searchsorted(key, qk, "left"), np.searchsorted(key, qk, "right")
+    offsets = np.zeros(len(qk) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum(hi - lo)
+    take = np.repeat(lo - offsets[:-1], hi - lo) + np.arange(offsets[-1], dtype=np.int64)
+    return rows[take], offsets
+
+
+def audience_main(model, args, ds, pool, vectors) -> dict:
+    """--audience_of: the --topk rows of the CSV that score each listed item (or each item of the two dataset pools) highest, to --out.
+    vectors: this run's encode_users rows [N, D] on the device, or None with --vectors_in."""
+    dev = torch.device(args.device)
+    N = len(ds)
+    if args.vectors_in:
+        with np.load(args.vectors_in) as f:
+            if not {"user_id", "domain_id", "vectors"} <= set(f.files):
+                raise SystemExit(f"{args.vectors_in}: not a file --vectors_out wrote (user_id, domain_id, vectors)")
+            uid, dom_in, vec = f["user_id"], f["domain_id"], f["vectors"]
+        if vec.ndim != 2 or vec.shape[0] != N or uid.shape != (N,) or not np.array_equal(uid, ds.user_nodes) \
+                or not np.array_equal(dom_in, ds.domain_id):
+            raise SystemExit(f"{args.vectors_in} does not match the users CSV: it holds {vec.shape[0]} rows, the CSV {N}; the row count, "
+                             f"the user_id column and the domain_id column must be the CSV's")
+        if vec.shape[1] != args.emb_dim:
+            raise SystemExit(f"{args.vectors_in}: vectors of {vec.shape[1]} elements, --emb_dim is {args.emb_dim}")
+        vectors = torch.from_numpy(np.ascontiguousarray(vec, dtype=np.float32)).to(dev)
+    if args.audience_of == "all":
+        if pool is None:
+            raise SystemExit("--audience_of all takes the items of the two dataset pools: use --pool dataset, or list the items in a FILE")
+        items = torch.cat(pool)
+        item_dom = torch.cat((torch.zeros_like(pool[0]), torch.ones_like(pool[1])))
+    else:
+        it, dm = listed_items(args.audience_of)
+        items, item_dom = torch.from_numpy(it).to(dev), torch.from_numpy(dm).to(dev)
+    holders = None
+    if args.exclude_holders:
+        idx, off = holders_of(items.cpu().numpy(), item_dom.cpu().numpy(), ds.seq_d1, ds.seq_d2, ds.i_node, ds.domain_id)
+        holders = (torch.from_numpy(idx).to(dev), torch.from_numpy(off).to(dev))
+    rows, scores = model.recommend_users(items, item_dom, vectors, torch.from_numpy(ds.domain_id).to(dev), k=args.topk, holders=holders)
+    rows = rows.cpu().numpy()
+    users = np.where(rows >= 0, ds.user_nodes[np.maximum(rows, 0)], -1)
+    out = {"item_id": items.cpu().numpy(), "domain_id": item_dom.cpu().numpy(), "users": users, "rows": rows, "scores": scores.cpu().numpy()}
+    write_npz(args.out, out)
+    print(f"wrote {args.out}: the {args.topk} best of {N} rows for {items.numel()} items"
+          + (", holders left out" if args.exclude_holders else ""))
+    return out
+
+
 def load_weights(model, path: str) -> str:
     """Load `path` into the model; returns what it was ("training state" / "state dict")."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
@@ -120,6 +205,10 @@ def main(argv=None):
         raise SystemExit(f"recommend.py with a joint job (-dm {args.domain_type}) is not supported: recommend for one dataset per run")
     if not 1 <= args.topk <= 256:
         raise SystemExit(f"--topk must be in 1..256, got {args.topk}")
+    if args.audience_of and args.similar_items:
+        raise SystemExit("--audience_of and --similar_items both write --out: one of them per run")
+    if (args.vectors_in or args.exclude_holders) and not args.audience_of:
+        raise SystemExit("--vectors_in and --exclude_holders belong to --audience_of")
     cls = {"gru4rec": GRU4Rec, "sasrec": SASRec, "bert4rec": BERT4Rec}.get(args.model.lower())
     if cls is None:
         raise SystemExit(f"unknown --model {args.model!r} (gru4rec | sasrec | bert4rec)")
@@ -154,6 +243,18 @@ def main(argv=None):
              "domain_id": torch.from_numpy(ds.domain_id[sel]).to(dev)}
     N = len(ds)
     vectors = None
+    if args.audience_of:
+        enc = None
+        if args.vectors_out or not args.vectors_in:
+            enc = model.encode_users(users, use_graph=not args.no_graph).reshape(-1, args.emb_dim)[:N]
+        if args.vectors_out:
+            vectors = enc.cpu().numpy()
+            write_npz(args.vectors_out, {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy(), "vectors": vectors})
+            print(f"wrote {args.vectors_out}: the scorer's vectors of {N} rows")
+        out = audience_main(model, args, ds, pool, enc)
+        if vectors is not None:
+            out["vectors"] = vectors
+        return out
     if args.vectors_out:
         vectors = model.encode_users(users, use_graph=not args.no_graph).reshape(-1, args.emb_dim)[:N].cpu().numpy()
         write_npz(args.vectors_out, {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy(), "vectors": vectors})

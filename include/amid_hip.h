@@ -1165,6 +1165,37 @@ int amid_neighbors_f32(const float* queries, const long long* query_ids, int Q, 
                        const long long* pool, long long n_pool, int metric, int k, int exclude_self, void* workspace, int* flags,
                        long long* ids, float* scores, void* stream);
 
+/* ---- audience top-K: the k stored user vectors that score an item highest (csrc/audience.hip) ---------------------------------------------------
+ * amid_topk_f32's question the other way round.  The candidates are rows of vectors [n_vectors, D] (contiguous fp32: encode_users' rows,
+ * say), each of domain 0 or 1, handed over as the two ascending int32 row lists slots_d1 [n_d1] (domain 0) and slots_d2 [n_d2] (domain 1); a
+ * list with no rows may be null.  The queries are Q items: items[q] a row of table [n_rows, D], item_domain[q] its domain (!= 0: domain 1).
+ * The score is predictModule's p(u, c) = sigmoid(w2 relu((W1[:, :D] u + b1) + W1[:, D:] table[c]) + b2): the same device functions in the
+ * same order as amid_topk_f32 (the two halves meet in one commutative fp32 addition), so a score is bit-identical to amid_topk_f32's for the
+ * same vector and the same table row.
+ * amid_audience_halves_f32: W1[:, :D] vectors[r] + b1 of every listed row into the head of the workspace, [n_d1 + n_d2][hid] -- once per set
+ * of vectors and weights; where it lies depends on nothing else, so one call serves every later amid_audience_topk_f32 on the same workspace
+ * and lists, whatever its Q and k.  A slot outside [0, n_vectors) raises AMID_FLAG_INDEX_RANGE in *flags and is not dereferenced.
+ * amid_audience_topk_f32: rows / scores [Q, k]: the k best rows of slots_dom(q) minus holders(q), best first, ties to the lower row; fewer than
+ * k candidates: row -1, score -inf.  holders(q) = holders[holders_off[q] .. holders_off[q + 1]) (holders null: none): row indices in ascending
+ * order, duplicates allowed; entries that are no candidate of the query's domain are ignored.  An items[q] outside [0, n_rows) raises
+ * AMID_FLAG_INDEX_RANGE and gives a row of the result that must not be used.  Three launches (the queries' item halves, the per-range lists,
+ * the merge).
+ * 1 <= k <= 256; D 64 / 128, hid 16 / 32 / 64 (else AMID_ERR_UNSUPPORTED); null pointers, Q <= 0, n_d1 or n_d2 < 0, both 0, n_d1 + n_d2 or
+ * n_vectors >= 2^31 - 1, n_rows <= 0, holders without holders_off: AMID_ERR_ARG; both before any device call.  Launches on the stream only, no
+ * host read.  workspace: amid_audience_workspace_bytes(Q, n_d1, n_d2, hid, k) bytes (negative: bad sizes or hid; non-decreasing in every
+ * argument); the halves launch needs (n_d1 + n_d2) * hid * 4 of them.
+ * amid_audience_target_workgroups(wgs): how many workgroups the top-K launch aims at when it cuts the tiles of 256 rows into ranges (default
+ * 1024; 1 .. 1024, anything below 1 restores the default); returns the value before.  Process-wide and not a tuning knob: the tests use it to
+ * reach ranges of several tiles at small sizes (1: one range walks every tile).  The results do not depend on it. */
+long long amid_audience_workspace_bytes(int Q, int n_d1, int n_d2, int hid, int k);
+int amid_audience_target_workgroups(int wgs);
+int amid_audience_halves_f32(const float* vectors, long long n_vectors, const int* slots_d1, int n_d1, const int* slots_d2, int n_d2,
+                             const float* w1, const float* b1, int D, int hid, void* workspace, int* flags, void* stream);
+int amid_audience_topk_f32(const long long* items, const long long* item_domain, int Q, const float* table, long long n_rows,
+                           const float* w1, const float* w2, const float* b2, const int* slots_d1, int n_d1, const int* slots_d2, int n_d2,
+                           const int* holders, const long long* holders_off, int D, int hid, int k, void* workspace, int* flags,
+                           long long* rows, float* scores, void* stream);
+
 /* ---- BERT4Rec strips on bf16 pieces (round 5; csrc/bert_strip.hip MODE 3) ------------------------------------------------------------------
  * The strip launches of a TransformerBlock (model_seq.py:242-245 and its autograd) with every product as six bf16 piece pairs at fp32
  * accuracy -- what SASRec's strips run on since round 4.  Each 128 x 128 weight TILE a chain multiplies with is a three-plane fragment image
