@@ -5,6 +5,7 @@ amid_topk_items_f32 / amid_topk_users_f32), and the history sets come from the p
 from __future__ import annotations
 
 import ctypes
+from typing import Optional
 
 import torch
 
@@ -182,3 +183,49 @@ class TopkMixin:
         lib().call("amid_audience_topk_f32", items.data_ptr(), item_domain.data_ptr(), Q, self.table.data_ptr(), self.n_rows, sc["w1"],
                    sc["w2"], sc["b2"], s1.data_ptr() if s1.numel() else None, s1.numel(), s2.data_ptr() if s2.numel() else None, s2.numel(),
                    hold, hold_off, self.D, self.hid, int(k), ws.data_ptr(), err.data_ptr(), rows.data_ptr(), scores.data_ptr(), self.s)
+
+    # ------------------------------------------------------------------ ranking each row's own candidate list (csrc/rank_lists.hip)
+    def _rank_lists_workspace(self, B: int, n_cand: int, k: int) -> torch.Tensor:
+        nbytes = int(lib().value("amid_rank_lists_workspace_bytes", B, n_cand, self.hid, k))
+        if nbytes < 0:
+            raise ValueError(f"rank lists: bad sizes B {B}, candidates {n_cand}, k {k}")
+        ws = getattr(self, "_rl_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            if ws is not None:
+                ws.record_stream(self.stream)          # (launches still queued on the engine's stream may read the old one)
+            with torch.cuda.stream(self.stream):
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._rl_ws = ws
+        return ws
+
+    def enqueue_own_sets(self, seq_d1: torch.Tensor, seq_d2: torch.Tensor, domain: torch.Tensor):
+        """own(b) = the sorted unique ids of row b's own-domain sequence (seq_d1 / seq_d2 [B, T] int64, domain [B]) as amid_topk_f32's
+        history triple (own, own_off, rows), formed on the device (amid_own_from_seq_i64).  Nothing is synchronised."""
+        B, T = seq_d1.shape
+        with torch.cuda.stream(self.stream):
+            own = torch.empty(B * T, dtype=torch.int64, device=self.device)
+            own_off = torch.empty(B + 1, dtype=torch.int32, device=self.device)
+            cnt = torch.empty(B, dtype=torch.int32, device=self.device)
+            rows = torch.arange(B, dtype=torch.int32, device=self.device)
+        lib().call("amid_own_from_seq_i64", seq_d1.data_ptr(), seq_d2.data_ptr(), domain.data_ptr(), B, T, cnt.data_ptr(), own.data_ptr(),
+                   own_off.data_ptr(), self.s)
+        return own, own_off, rows
+
+    def enqueue_rank_lists(self, u: torch.Tensor, u_dom_stride: int, domain: torch.Tensor, cand: torch.Tensor, cand_off: torch.Tensor,
+                           n_cand: int, own: Optional[torch.Tensor], own_off: Optional[torch.Tensor], rows: Optional[torch.Tensor], k,
+                           list_scores: Optional[torch.Tensor], ids: Optional[torch.Tensor], scores: Optional[torch.Tensor],
+                           positions: Optional[torch.Tensor], err: torch.Tensor) -> None:
+        """amid_rank_lists_f32 on the engine's stream: row b's vector (u + domain[b] * u_dom_stride + b * D floats: what
+        enqueue_user_vectors returns fits, or [B, D] vectors with stride 0) against its own list cand[cand_off[b] : cand_off[b + 1]]
+        (cand int64 [n_cand], cand_off int64 [B + 1] on the device, n_cand the host's copy of cand_off[B]).  list_scores [n_cand] or None;
+        ids / scores / positions [B, k] or all None (k is then ignored); own / own_off / rows: amid_topk_f32's history triple or None;
+        err [1] int32 flags.  Nothing is synchronised."""
+        B = domain.shape[0]
+        k = int(k) if ids is not None else 0
+        ws = self._rank_lists_workspace(B, int(n_cand), k)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()       # noqa: E731
+        lib().call("amid_rank_lists_f32", u.data_ptr(), int(u_dom_stride), domain.data_ptr(), B, ptr(cand), cand_off.data_ptr(), int(n_cand),
+                   ptr(own), None if own is None else own_off.data_ptr(), None if own is None else rows.data_ptr(), self.table.data_ptr(),
+                   self.n_rows, *self._scorer().values(), self.D, self.hid, k, ws.data_ptr(), err.data_ptr(), ptr(list_scores),
+                   None if ids is None else ids.data_ptr(), None if scores is None else scores.data_ptr(),
+                   None if positions is None else positions.data_ptr(), self.s)

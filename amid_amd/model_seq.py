@@ -35,6 +35,7 @@ before the encoders, which then run over 2 * seq_len tokens (csrc/innercomp.hip)
 from __future__ import annotations
 
 import weakref
+from collections import namedtuple
 from typing import Dict, Optional
 
 import torch
@@ -43,6 +44,9 @@ import torch.nn as nn
 from ._lib import lib, ptr_array
 from .engine import SASREC_LN_EPS, SasrecEngine
 from .engine_bert import Bert4recEngine
+
+# what rank_candidates / rank_candidates_from_vectors return: device tensors, a field not asked for is None
+RankedLists = namedtuple("RankedLists", ["ids", "scores", "positions", "list_scores"])
 
 
 def _register_tree(root: nn.Module, dotted: str, param: nn.Parameter) -> None:
@@ -671,6 +675,144 @@ class SASRec(nn.Module):
         torch.cuda.current_stream().wait_stream(eng.stream)
         eng.check_index_error(flags)
         return rows, scores
+
+    RANK_LISTS_ROWS = 65536           # rows per amid_rank_lists_f32 call at most (the workspace holds a partial list per row and more)
+    RANK_LISTS_CANDS = 1 << 26        # candidates per call at most, unless one row alone holds more
+
+    def _candidate_lists(self, candidates, B: int, who: str):
+        """`candidates` as (items int64 [n] on the device, offsets int64 [B + 1] on the device, the offsets on the host): a pair
+        (items [n], offsets [B + 1]) -- validated on the host as recommend_users validates holders -- or a [B, C] tensor."""
+        dev = self.engine.device
+        if isinstance(candidates, (tuple, list)):
+            if len(candidates) != 2:
+                raise ValueError(f"{who}: candidates is a pair (items [n], offsets [B + 1]) or a [B, C] tensor")
+            items = torch.as_tensor(candidates[0]).to(dev, torch.int64).reshape(-1).contiguous()
+            off = torch.as_tensor(candidates[1]).to(torch.int64).reshape(-1)
+            if off.numel() != B + 1:
+                raise ValueError(f"{who}: the candidates' offsets must have B + 1 = {B + 1} entries, got {off.numel()}")
+            off_h = off.cpu()
+            if int(off_h[0]) != 0 or int(off_h[-1]) != items.numel() or bool((off_h[1:] < off_h[:-1]).any()):
+                raise ValueError(f"{who}: the candidates' offsets must rise from 0 to the number of items")
+            return items, off.to(dev).contiguous(), off_h
+        c = torch.as_tensor(candidates)
+        if c.dim() != 2 or c.shape[0] != B:
+            raise ValueError(f"{who}: candidates is a pair (items [n], offsets [B + 1]) or a [B, C] tensor with B = {B} rows")
+        off_h = torch.arange(B + 1, dtype=torch.int64) * c.shape[1]
+        return c.to(dev, torch.int64).reshape(-1).contiguous(), off_h.to(dev), off_h
+
+    def _rank_lists(self, u, u_dom_stride: int, dom, items, off, off_h, k, own, want_scores: bool, flags) -> "RankedLists":
+        """The calls of one ranking on the engine's stream: rows in chunks of at most RANK_LISTS_ROWS rows and RANK_LISTS_CANDS
+        candidates (cut on the host from the host's offsets; a row's result depends on its own list only, so not on the cut)."""
+        eng = self.engine
+        dev, B, D, n = eng.device, dom.shape[0], eng.D, int(items.numel())
+        ids = scores = pos = ls = None
+        if k is not None:
+            ids = torch.empty(B, k, dtype=torch.int64, device=dev)
+            scores = torch.empty(B, k, dtype=torch.float32, device=dev)
+            pos = torch.empty(B, k, dtype=torch.int64, device=dev)
+        if want_scores:
+            ls = torch.empty(n, dtype=torch.float32, device=dev)
+        uf = u.reshape(-1)
+        c0 = 0
+        while c0 < B:
+            c1 = min(B, c0 + self.RANK_LISTS_ROWS)
+            o0 = int(off_h[c0])
+            while c1 > c0 + 1 and int(off_h[c1]) - o0 > self.RANK_LISTS_CANDS:
+                c1 = c0 + max(1, (c1 - c0) // 2)
+            o1 = int(off_h[c1])
+            if o1 - o0 >= 2 ** 31 - 1:
+                raise ValueError("rank lists: a list holds at most 2^31 - 2 candidates")
+            if k is None and o1 == o0:                       # (scores only, and no candidate in these rows: nothing to write)
+                c0 = c1
+                continue
+            sl = (lambda t: None if t is None else t[c0:c1])
+            if c0 == 0 and c1 == B:
+                off_c = off
+            else:
+                with torch.cuda.stream(eng.stream):          # (the chunk's offsets count from its first candidate)
+                    off_c = off[c0:c1 + 1] - o0
+            eng.enqueue_rank_lists(uf[c0 * D:], u_dom_stride, dom[c0:c1], items[o0:o1], off_c, o1 - o0,
+                                   None if own is None else own[0], None if own is None else own[1], None if own is None else own[2][c0:c1],
+                                   k, None if ls is None else ls[o0:o1], sl(ids), sl(scores), sl(pos), flags.err)
+            c0 = c1
+        return RankedLists(ids, scores, pos, ls)
+
+    @staticmethod
+    def _check_rank_k(k, list_scores: bool, who: str):
+        if k is None:
+            if not list_scores:
+                raise ValueError(f"{who}: k=None asks for the lists' scores only, so list_scores must be true")
+            return None
+        if not 1 <= int(k) <= 256:
+            raise ValueError(f"k must be in 1..256 or None, got {k}")
+        return int(k)
+
+    @torch.no_grad()
+    def rank_candidates_from_vectors(self, u, domain_id, candidates, k=10, history=None, list_scores: bool = False) -> "RankedLists":
+        """The scorer alone over each row's OWN candidate list: stored user vectors u [B, D] (encode_users' rows; any B), the domain
+        domain_id [B], and candidates -- a pair (items int64 [n], offsets int64 [B + 1]): row b's list is items[offsets[b] :
+        offsets[b + 1]], possibly empty, duplicates allowed -- or a [B, C] tensor of C candidates a row.  Returns
+        RankedLists(ids, scores, positions, list_scores) of device tensors: the k best entries of each list ([B, k]; larger score
+        first, ties to the lower id, further ties to the lower position; positions: the entry's index inside its own list; padded
+        with -1 / -inf / -1), minus the ids of history [B, T] when given; and with list_scores=True every entry's score ([n], whatever
+        history says).  k=None: the scores only.  A field not asked for is None.  A score equals recommend_from_vectors' for the same
+        vector and item bit for bit (csrc/rank_lists.hip)."""
+        eng = self.engine
+        dev = eng.device
+        who = "rank_candidates_from_vectors"
+        u = torch.as_tensor(u).to(dev, torch.float32).contiguous()
+        if u.dim() != 2 or u.shape[1] != eng.D or u.shape[0] < 1:
+            raise ValueError(f"{who}: u must be [B, {eng.D}] vectors")
+        B = u.shape[0]
+        dom = torch.as_tensor(domain_id).to(dev, torch.int64).reshape(B).contiguous()
+        k = self._check_rank_k(k, list_scores, who)
+        items, off, off_h = self._candidate_lists(candidates, B, who)
+        if history is not None:
+            history = torch.as_tensor(history).to(dev, torch.int64).contiguous()
+            if history.dim() != 2 or history.shape[0] != B:
+                raise ValueError(f"{who}: history must be [B, T] item ids")
+        if eng.table_m is not None:
+            eng.flush_table()
+        flags = eng.flags_holder()
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        own = None if history is None or k is None else eng.enqueue_own_sets(history, history, dom)
+        out = self._rank_lists(u, 0, dom, items, off, off_h, k, own, bool(list_scores), flags)
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(flags)
+        return out
+
+    @torch.no_grad()
+    def rank_candidates(self, seq_d1, seq_d2, domain_id, candidates, k=10, exclude_history: bool = False,
+                        list_scores: bool = False) -> "RankedLists":
+        """rank_candidates_from_vectors for rows given as sequences (seq_d1 / seq_d2 [B, T], domain_id [B]): the rows are encoded as
+        recommend() encodes them (comp models need exactly bs rows), so the result equals encode_users followed by
+        rank_candidates_from_vectors bit for bit.  exclude_history leaves the ids of the row's own-domain sequence out of the top-K
+        (off by default: the list is the caller's)."""
+        eng = self.engine
+        dev = eng.device
+        who = "rank_candidates"
+        seq_d1 = torch.as_tensor(seq_d1).to(dev, torch.int64).contiguous()
+        seq_d2 = torch.as_tensor(seq_d2).to(dev, torch.int64).contiguous()
+        if seq_d1.dim() != 2 or seq_d1.shape != seq_d2.shape:
+            raise ValueError(f"{who}: seq_d1 and seq_d2 must be [B, T] tensors of one shape")
+        B, T = seq_d1.shape
+        dom = torch.as_tensor(domain_id).to(dev, torch.int64).reshape(B).contiguous()
+        self._check_comp_batch(B)
+        k = self._check_rank_k(k, list_scores, who)
+        items, off, off_h = self._candidate_lists(candidates, B, who)
+        if eng.table_m is not None:
+            eng.flush_table()
+        zero = torch.zeros(B, dtype=torch.int64, device=dev)
+        label = torch.zeros(B, 2, device=dev)
+        pl = eng.plan(B, T, 2, need_grad=False)              # recommend()'s plan
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        eng.load_batch(pl, zero, zero.view(B, 1), seq_d1, seq_d2, label, dom)
+        u, stride = eng.enqueue_user_vectors(pl)
+        own = eng.enqueue_own_sets(seq_d1, seq_d2, dom) if exclude_history and k is not None else None
+        out = self._rank_lists(u, stride, dom, items, off, off_h, k, own, bool(list_scores), pl)
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(pl)
+        return out
 
     def check_indices(self) -> None:
         """Raise IndexError if any batch since the last check carried an item id outside the table (nn.Embedding raises on the spot,

@@ -24,16 +24,27 @@ Takes the model flags of ``train_sr.py`` (``--model --emb_dim --hid_dim --seq_le
                             dataset pools (--pool dataset), each in its pool's domain; FILE: "item_id domain_id" pairs (text, or a .npy
                             array [M, 2]).  Written: item_id [M], domain_id [M], users [M, K] (the rows' user_id, -1 where the domain ran
                             out of rows), rows [M, K] (CSV row numbers), scores [M, K]
-    --vectors_in FILE.npz   with --audience_of: take the rows' vectors from a file --vectors_out wrote for the same CSV instead of
-                            encoding them in this run
+    --vectors_in FILE.npz   with --audience_of or --candidates: take the rows' vectors from a file --vectors_out wrote for the same CSV
+                            instead of encoding them in this run
     --exclude_holders       with --audience_of: leave out of an item's audience every row whose own-domain history, the held-out item
                             included, contains the item
+    --candidates FILE       instead of recommendations over a shared pool, rank each row's OWN candidate list
+                            (SASRec.rank_candidates_from_vectors: an upstream retriever's output, an in-stock list, a hand-built negative
+                            set).  FILE: an .npz with offsets [N + 1] and items [n] in the row order of --users (row r's list is
+                            items[offsets[r] : offsets[r + 1]]; a user_id [N] array, if present, must equal the CSV's column), or a text
+                            file with one line per CSV row, ids separated by whitespace or commas, an empty line an empty list.  Written:
+                            user_id [N], domain_id [N], items [N, K] (-1 where the list ran out), scores [N, K], positions [N, K] (the
+                            entry's index inside its row's list)
+    --exclude_history       with --candidates: leave the ids of the row's own-domain sequence (under --history full the held-out item
+                            too) out of its top-K.  Off by default: the list is the caller's
+    --list_scores           with --candidates: also write offsets [N + 1], list_items [n] and list_scores [n], every entry's score
 
     python recommend.py --data_root /path/to/AMID -ds amazon -dm cloth_sport --overlap_ratio 0.75 --model sasrec --bs 256 \
         --seq_len 50 --emb_dim 128 --weights runs/seed0/best_d1.pt --topk 10 --out cloth_sport_top10.npz
     python recommend.py ... --weights runs/seed0/best_d1.pt --vectors_out cloth_sport_users.npz
     python recommend.py ... --weights runs/seed0/best_d1.pt --similar_items all --metric cosine --topk 20 --out cloth_sport_similar.npz
     python recommend.py ... --weights runs/seed0/best_d1.pt --audience_of all --exclude_holders --topk 100 --out cloth_sport_audiences.npz
+    python recommend.py ... --weights runs/seed0/best_d1.pt --candidates retrieved.npz --exclude_history --topk 20 --out cloth_sport_reranked.npz
 
 Every row of the CSV gets a recommendation: the last batch is filled with rows from the start of the CSV (comp models need whole
 ``--bs``-row batches) and the surplus is cut off.  The ranking is ``SASRec.recommend_all``: one graph replay a batch.
@@ -68,6 +79,9 @@ def build_parser():
     p.add_argument("--audience_of", type=str, default=None, help="all | FILE of 'item_id domain_id' pairs: write their --topk users to --out instead")
     p.add_argument("--vectors_in", type=str, default=None, help="FILE.npz that --vectors_out wrote for --users: the vectors --audience_of ranks")
     p.add_argument("--exclude_holders", action="store_true", help="--audience_of: leave out the rows whose history holds the item")
+    p.add_argument("--candidates", type=str, default=None, help="FILE.npz (offsets, items) or text, a line a row: rank each row's own list to --out instead")
+    p.add_argument("--exclude_history", action="store_true", help="--candidates: leave the row's own-domain history out of its top-K")
+    p.add_argument("--list_scores", action="store_true", help="--candidates: also write the score of every entry of every list")
     return p
 
 
@@ -150,23 +164,77 @@ def holders_of(items: np.ndarray, item_dom: np.ndarray, seq_d1: np.ndarray, seq_
     return rows[take], offsets
 
 
+def load_vectors(args, ds) -> torch.Tensor:
+    """--vectors_in: the vectors [N, D] of a file --vectors_out wrote for this CSV, on the device; SystemExit if it is another CSV's."""
+    N = len(ds)
+    with np.load(args.vectors_in) as f:
+        if not {"user_id", "domain_id", "vectors"} <= set(f.files):
+            raise SystemExit(f"{args.vectors_in}: not a file --vectors_out wrote (user_id, domain_id, vectors)")
+        uid, dom_in, vec = f["user_id"], f["domain_id"], f["vectors"]
+    if vec.ndim != 2 or vec.shape[0] != N or uid.shape != (N,) or not np.array_equal(uid, ds.user_nodes) \
+            or not np.array_equal(dom_in, ds.domain_id):
+        raise SystemExit(f"{args.vectors_in} does not match the users CSV: it holds {vec.shape[0]} rows, the CSV {N}; the row count, "
+                         f"the user_id column and the domain_id column must be the CSV's")
+    if vec.shape[1] != args.emb_dim:
+        raise SystemExit(f"{args.vectors_in}: vectors of {vec.shape[1]} elements, --emb_dim is {args.emb_dim}")
+    return torch.from_numpy(np.ascontiguousarray(vec, dtype=np.float32)).to(torch.device(args.device))
+
+
+def candidate_lists(path: str, n_rows: int, user_ids: np.ndarray):
+    """--candidates FILE as (items int64 [n], offsets int64 [n_rows + 1]): an .npz with `offsets` and `items` (and optionally `user_id`,
+    which must be the CSV's column), or a text file with one line per CSV row (ids separated by whitespace or commas; an empty line is an
+    empty list).  SystemExit where the file does not fit the CSV's n_rows rows."""
+    if path.endswith(".npz"):
+        with np.load(path) as f:
+            if not {"offsets", "items"} <= set(f.files):
+                raise SystemExit(f"{path}: expected the arrays offsets [N + 1] and items [n]")
+            offsets, items = f["offsets"].astype(np.int64).reshape(-1), f["items"].astype(np.int64).reshape(-1)
+            uid = f["user_id"] if "user_id" in f.files else None
+    else:
+        with open(path) as f:
+            lines = f.read().split("\n")
+        if lines and lines[-1] == "":
+            lines.pop()                                                                    # (the newline that ends the last row)
+        rows = [[int(x) for x in ln.replace(",", " ").split()] for ln in lines]
+        offsets = np.zeros(len(rows) + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([len(r) for r in rows])
+        items = np.array([x for r in rows for x in r], dtype=np.int64)
+        uid = None
+    if offsets.size != n_rows + 1:
+        raise SystemExit(f"{path} holds the lists of {max(offsets.size - 1, 0)} rows, the users CSV has {n_rows}")
+    if offsets[0] != 0 or offsets[-1] != items.size or (np.diff(offsets) < 0).any():
+        raise SystemExit(f"{path}: offsets must rise from 0 to the number of items ({items.size})")
+    if uid is not None and (uid.shape != (n_rows,) or not np.array_equal(uid, user_ids)):
+        raise SystemExit(f"{path} does not match the users CSV: its user_id array is not the CSV's user_id column")
+    return items, offsets
+
+
+def candidates_main(model, args, ds, vectors, history) -> dict:
+    """--candidates: the --topk best entries of each row's own list, to --out.  vectors: the rows' vectors [N, D] on the device;
+    history: [N, T] ids to leave out (--exclude_history) or None."""
+    dev = torch.device(args.device)
+    N = len(ds)
+    items, offsets = candidate_lists(args.candidates, N, ds.user_nodes)
+    res = model.rank_candidates_from_vectors(vectors, torch.from_numpy(ds.domain_id).to(dev),
+                                             (torch.from_numpy(items).to(dev), torch.from_numpy(offsets)), k=args.topk, history=history,
+                                             list_scores=args.list_scores)
+    out = {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy(), "items": res.ids.cpu().numpy(),
+           "scores": res.scores.cpu().numpy(), "positions": res.positions.cpu().numpy()}
+    if args.list_scores:
+        out.update(offsets=offsets, list_items=items, list_scores=res.list_scores.cpu().numpy())
+    write_npz(args.out, out)
+    print(f"wrote {args.out}: top-{args.topk} of the own lists of {N} rows ({items.size} candidates)"
+          + (", histories left out" if args.exclude_history else ""))
+    return out
+
+
 def audience_main(model, args, ds, pool, vectors) -> dict:
     """--audience_of: the --topk rows of the CSV that score each listed item (or each item of the two dataset pools) highest, to --out.
     vectors: this run's encode_users rows [N, D] on the device, or None with --vectors_in."""
     dev = torch.device(args.device)
     N = len(ds)
     if args.vectors_in:
-        with np.load(args.vectors_in) as f:
-            if not {"user_id", "domain_id", "vectors"} <= set(f.files):
-                raise SystemExit(f"{args.vectors_in}: not a file --vectors_out wrote (user_id, domain_id, vectors)")
-            uid, dom_in, vec = f["user_id"], f["domain_id"], f["vectors"]
-        if vec.ndim != 2 or vec.shape[0] != N or uid.shape != (N,) or not np.array_equal(uid, ds.user_nodes) \
-                or not np.array_equal(dom_in, ds.domain_id):
-            raise SystemExit(f"{args.vectors_in} does not match the users CSV: it holds {vec.shape[0]} rows, the CSV {N}; the row count, "
-                             f"the user_id column and the domain_id column must be the CSV's")
-        if vec.shape[1] != args.emb_dim:
-            raise SystemExit(f"{args.vectors_in}: vectors of {vec.shape[1]} elements, --emb_dim is {args.emb_dim}")
-        vectors = torch.from_numpy(np.ascontiguousarray(vec, dtype=np.float32)).to(dev)
+        vectors = load_vectors(args, ds)
     if args.audience_of == "all":
         if pool is None:
             raise SystemExit("--audience_of all takes the items of the two dataset pools: use --pool dataset, or list the items in a FILE")
@@ -207,8 +275,14 @@ def main(argv=None):
         raise SystemExit(f"--topk must be in 1..256, got {args.topk}")
     if args.audience_of and args.similar_items:
         raise SystemExit("--audience_of and --similar_items both write --out: one of them per run")
-    if (args.vectors_in or args.exclude_holders) and not args.audience_of:
-        raise SystemExit("--vectors_in and --exclude_holders belong to --audience_of")
+    if args.candidates and (args.audience_of or args.similar_items):
+        raise SystemExit("--candidates, --audience_of and --similar_items all write --out: one of them per run")
+    if args.exclude_holders and not args.audience_of:
+        raise SystemExit("--exclude_holders belongs to --audience_of")
+    if args.vectors_in and not (args.audience_of or args.candidates):
+        raise SystemExit("--vectors_in belongs to --audience_of or --candidates")
+    if (args.exclude_history or args.list_scores) and not args.candidates:
+        raise SystemExit("--exclude_history and --list_scores belong to --candidates")
     cls = {"gru4rec": GRU4Rec, "sasrec": SASRec, "bert4rec": BERT4Rec}.get(args.model.lower())
     if cls is None:
         raise SystemExit(f"unknown --model {args.model!r} (gru4rec | sasrec | bert4rec)")
@@ -243,7 +317,7 @@ def main(argv=None):
              "domain_id": torch.from_numpy(ds.domain_id[sel]).to(dev)}
     N = len(ds)
     vectors = None
-    if args.audience_of:
+    if args.audience_of or args.candidates:
         enc = None
         if args.vectors_out or not args.vectors_in:
             enc = model.encode_users(users, use_graph=not args.no_graph).reshape(-1, args.emb_dim)[:N]
@@ -251,7 +325,11 @@ def main(argv=None):
             vectors = enc.cpu().numpy()
             write_npz(args.vectors_out, {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy(), "vectors": vectors})
             print(f"wrote {args.vectors_out}: the scorer's vectors of {N} rows")
-        out = audience_main(model, args, ds, pool, enc)
+        if args.candidates:
+            history = torch.from_numpy(np.where(ds.domain_id[:, None] != 0, s2, s1)).to(dev) if args.exclude_history else None
+            out = candidates_main(model, args, ds, load_vectors(args, ds) if args.vectors_in else enc, history)
+        else:
+            out = audience_main(model, args, ds, pool, enc)
         if vectors is not None:
             out["vectors"] = vectors
         return out

@@ -1196,6 +1196,41 @@ int amid_audience_topk_f32(const long long* items, const long long* item_domain,
                            const int* holders, const long long* holders_off, int D, int hid, int k, void* workspace, int* flags,
                            long long* rows, float* scores, void* stream);
 
+/* ---- ranking each row's own candidate list (csrc/rank_lists.hip) ---------------------------------------------------------------------------------
+ * B rows, each with a list of its own: row b's vector is u + domain(b) * u_dom_stride + b * D (amid_topk_f32's convention, domain(b) =
+ * domain_id[b] != 0), its list cand[cand_off[b] .. cand_off[b + 1]) -- cand_off [B + 1] int64 on the device, n_cand the host's copy of
+ * cand_off[B].  A list may be empty (cand may be null when n_cand is 0) and may hold an id more than once.  Every offset is clamped into
+ * [0, n_cand]; an offset outside, or a falling pair (an empty list), raises AMID_FLAG_INDEX_RANGE in *flags; nothing outside
+ * cand[0 .. n_cand) is dereferenced.  Offsets that do not rise can name lists that overlap; they are ranked as they stand while their tiles
+ * fit what the workspace was sized for from B and n_cand (rising offsets always do), beyond that the later rows lose entries or come out as
+ * padding and the flag is raised: nothing is written outside the workspace.  The score is predictModule's p(u, c) = sigmoid(w2 relu((W1[:, :D] u + b1) + W1[:, D:] table[c]) + b2): the
+ * same device functions in the same order as amid_topk_f32 and amid_audience_topk_f32, so a score is bit-identical to theirs for the same
+ * vector and the same table row.  Nothing is shared between rows: every (row, entry) pair pays its own item half.
+ * list_scores [n_cand] (may be null): entry j's score, whatever the exclusion says; an id outside [0, n_rows) is not dereferenced, gets NaN
+ * and raises AMID_FLAG_INDEX_RANGE.
+ * ids / scores / positions [B, k] (all three or none; at least one of list_scores and the three): the k best entries of each list, larger
+ * score first, ties to the lower id, further ties to the lower position; positions: the entry's index inside its own list.  Fewer than k
+ * entries: id -1, score -inf, position -1.  Entries with a bad id never enter; with own_items non-null neither do entries whose id is in
+ * own(b) = own_items[own_off[rows[b]] .. own_off[rows[b] + 1]) (sorted unique ids: amid_topk_f32's triple, amid_own_from_seq_i64's output).
+ * The order is total over a list's entries: the result does not depend on how the lists were cut into tiles of 256 entries and units of
+ * tiles, or on which workgroup took which unit.  No float atomics.
+ * 1 <= k <= 256 when the three are given (k is ignored otherwise); D 64 / 128, hid 16 / 32 / 64 (else AMID_ERR_UNSUPPORTED); null u, domain_id,
+ * cand_off, table, weights, workspace or flags, cand null with n_cand > 0, B <= 0, n_cand < 0 or >= 2^31 - 1, n_rows <= 0, the three given
+ * partly, neither output, own_items without own_off or rows: AMID_ERR_ARG; both before any device call.  Three launches (per row: the user
+ * half, and the prefix of the rows' unit counts; the units' scores and lists; the merge) on the stream only, no host read, no allocation.
+ * workspace: amid_rank_lists_workspace_bytes(B, n_cand, hid, k) bytes, k = 0 for a call without the three (negative: bad sizes or hid;
+ * non-decreasing in every argument).
+ * amid_rank_lists_target_workgroups(wgs): how many units the score launch aims at when it cuts a row's tiles into units of consecutive tiles
+ * (default 2048; 1 .. 2048, anything below 1 restores the default); returns the value before.  Process-wide and not a tuning knob: the tests
+ * use it to reach units of several tiles at small sizes (1: one unit walks every tile of a row).  The results do not depend on it. */
+long long amid_rank_lists_workspace_bytes(int B, long long n_cand, int hid, int k);
+int amid_rank_lists_target_workgroups(int wgs);
+int amid_rank_lists_f32(const float* u, long long u_dom_stride, const long long* domain_id, int B, const long long* cand,
+                        const long long* cand_off, long long n_cand, const long long* own_items, const int* own_off, const int* rows,
+                        const float* table, long long n_rows, const float* w1, const float* b1, const float* w2, const float* b2, int D,
+                        int hid, int k, void* workspace, int* flags, float* list_scores, long long* ids, float* scores,
+                        long long* positions, void* stream);
+
 /* ---- BERT4Rec strips on bf16 pieces (round 5; csrc/bert_strip.hip MODE 3) ------------------------------------------------------------------
  * The strip launches of a TransformerBlock (model_seq.py:242-245 and its autograd) with every product as six bf16 piece pairs at fp32
  * accuracy -- what SASRec's strips run on since round 4.  Each 128 x 128 weight TILE a chain multiplies with is a three-plane fragment image
