@@ -24,6 +24,7 @@
 // is never offered), such a query has no candidates (its list stays empty: padding).
 #include <algorithm>
 #include "topk_list.h"
+#include "sim_parts.h"
 #include "amid_hip.h"
 
 namespace amid {
@@ -48,7 +49,7 @@ struct NbArgs {
     int* flags; long long* out_ids; float* out_s;
 };
 
-__device__ __forceinline__ f32x4 nb_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 nb_mfma(float a, float b, f32x4 c) { return sim_mfma(a, b, c); }       // (sim_parts.h: the arithmetic diversify.hip shares)
 __device__ __forceinline__ bool nb_id_ok(const NbArgs& a, long long id) { return id >= 0 && id < a.n_rows; }
 
 // ---- a wave's offer to a list ------------------------------------------------------------------------------------------------------------------
@@ -128,16 +129,7 @@ __global__ __launch_bounds__(FR_THREADS) void nb_norm_kernel(const NbArgs a) {
                 row = a.queries + q * D;
             }
         }
-        float ss = 0.f;
-        if (row != nullptr) {
-#pragma unroll
-            for (int i = 0; i < D / 32; ++i) {
-                const float4 v = ld4(row + part * (D / 8) + 4 * i);
-                ss = fmaf(v.x, v.x, ss); ss = fmaf(v.y, v.y, ss); ss = fmaf(v.z, v.z, ss); ss = fmaf(v.w, v.w, ss);
-            }
-        }
-        ss = group_sum<8>(ss);
-        const float inv = row != nullptr ? 1.0f / fmaxf(sqrtf(ss), 1e-8f) : 0.f;
+        const float inv = sim_inv_norm<D>(row, part);
         if (part == 0 && e < total) {
             if (e < a.n_cand) a.inv_c[e] = inv; else a.inv_q[e - a.n_cand] = inv;
         }
@@ -264,8 +256,8 @@ __global__ __launch_bounds__(FR_THREADS) void nb_scan_kernel(const NbArgs a) {
             float4 s0 = make_float4(acc0[0], acc0[1], acc0[2], acc0[3]), s1 = make_float4(acc1[0], acc1[1], acc1[2], acc1[3]);
             if (a.metric) {
                 const float4 i0 = ld4(cinv + c0), i1 = ld4(cinv + c1);
-                s0 = make_float4((s0.x * qinv) * i0.x, (s0.y * qinv) * i0.y, (s0.z * qinv) * i0.z, (s0.w * qinv) * i0.w);
-                s1 = make_float4((s1.x * qinv) * i1.x, (s1.y * qinv) * i1.y, (s1.z * qinv) * i1.z, (s1.w * qinv) * i1.w);
+                s0 = make_float4(sim_cosine(s0.x, qinv, i0.x), sim_cosine(s0.y, qinv, i0.y), sim_cosine(s0.z, qinv, i0.z), sim_cosine(s0.w, qinv, i0.w));
+                s1 = make_float4(sim_cosine(s1.x, qinv, i1.x), sim_cosine(s1.y, qinv, i1.y), sim_cosine(s1.z, qinv, i1.z), sim_cosine(s1.w, qinv, i1.w));
             }
             st4(sc + qrow * NB_LDSC + c0, s0);
             st4(sc + qrow * NB_LDSC + c1, s1);

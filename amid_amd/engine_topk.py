@@ -229,3 +229,30 @@ class TopkMixin:
                    self.n_rows, *self._scorer().values(), self.D, self.hid, k, ws.data_ptr(), err.data_ptr(), ptr(list_scores),
                    None if ids is None else ids.data_ptr(), None if scores is None else scores.data_ptr(),
                    None if positions is None else positions.data_ptr(), self.s)
+
+    # ------------------------------------------------------------------ diversified top-K: greedy MMR over each row's list (csrc/diversify.hip)
+    def _mmr_workspace(self, B: int, n_cand: int, k: int, shortlist: int) -> torch.Tensor:
+        nbytes = int(lib().value("amid_mmr_workspace_bytes", B, n_cand, self.D, k, shortlist))
+        if nbytes < 0:
+            raise ValueError(f"diversify: bad sizes B {B}, candidates {n_cand}, k {k}, shortlist {shortlist}, D {self.D}")
+        ws = getattr(self, "_mmr_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            if ws is not None:
+                ws.record_stream(self.stream)          # (launches still queued on the engine's stream may read the old one)
+            with torch.cuda.stream(self.stream):
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._mmr_ws = ws
+        return ws
+
+    def enqueue_mmr_lists(self, cand: torch.Tensor, cand_off: torch.Tensor, rel: torch.Tensor, n_cand: int, metric: str, lam: float, k: int,
+                          shortlist: int, ids: torch.Tensor, scores: torch.Tensor, values: torch.Tensor, max_sims: torch.Tensor,
+                          positions: torch.Tensor, err: torch.Tensor) -> None:
+        """amid_mmr_lists_f32 on the engine's stream over the item table: row b's list cand[cand_off[b] : cand_off[b + 1]] (cand int64
+        [n_cand], cand_off int64 [B + 1] on the device, n_cand the host's copy of cand_off[B]) with the relevance rel [n_cand] float32;
+        ids / scores / values / max_sims / positions [B, k]; err [1] int32 flags.  Nothing is synchronised."""
+        B = cand_off.shape[0] - 1
+        ws = self._mmr_workspace(B, int(n_cand), int(k), int(shortlist))
+        ptr = lambda t: None if t.numel() == 0 else t.data_ptr()                     # noqa: E731
+        lib().call("amid_mmr_lists_f32", ptr(cand), cand_off.data_ptr(), ptr(rel), int(n_cand), B, self.table.data_ptr(), self.n_rows, self.D,
+                   self.NEIGHBOR_METRICS[metric], float(lam), int(k), int(shortlist), ws.data_ptr(), err.data_ptr(), ids.data_ptr(),
+                   scores.data_ptr(), values.data_ptr(), max_sims.data_ptr(), positions.data_ptr(), self.s)

@@ -47,6 +47,7 @@ from .engine_bert import Bert4recEngine
 
 # what rank_candidates / rank_candidates_from_vectors return: device tensors, a field not asked for is None
 RankedLists = namedtuple("RankedLists", ["ids", "scores", "positions", "list_scores"])
+DiverseLists = namedtuple("DiverseLists", ["ids", "scores", "values", "max_sims", "positions"])
 
 
 def _register_tree(root: nn.Module, dotted: str, param: nn.Parameter) -> None:
@@ -813,6 +814,100 @@ class SASRec(nn.Module):
         torch.cuda.current_stream().wait_stream(eng.stream)
         eng.check_index_error(pl)
         return out
+
+    DIVERSIFY_ROWS = 65536            # rows per amid_mmr_lists_f32 call at most (the workspace holds a partial shortlist per row and more)
+    DIVERSIFY_CANDS = 1 << 26         # entries per call at most, unless one row alone holds more
+
+    @staticmethod
+    def _check_diversify(k, lam, shortlist, who: str):
+        if not 1 <= int(k) <= 256:
+            raise ValueError(f"k must be in 1..256, got {k}")
+        lam = float(lam)
+        if not 0.0 <= lam <= 1.0:                            # (false for a NaN)
+            raise ValueError(f"{who}: lam must be in [0, 1], got {lam}")
+        shortlist = min(256, max(int(k), 100)) if shortlist is None else int(shortlist)
+        if not int(k) <= shortlist <= 256:
+            raise ValueError(f"{who}: shortlist must be in k..256, got {shortlist} with k {k}")
+        return int(k), lam, shortlist
+
+    @torch.no_grad()
+    def diversify(self, candidates, relevance, k: int = 10, lam: float = 0.7, metric: str = "cosine", shortlist=None) -> "DiverseLists":
+        """Greedy Maximal Marginal Relevance over each row's OWN list (csrc/diversify.hip): candidates as rank_candidates_from_vectors
+        takes them -- a pair (items int64 [n], offsets int64 [B + 1]) or a [B, C] tensor --, relevance float32 [n] or [B, C], one per
+        entry (rank_candidates' list_scores fit: an entry with a NaN relevance is absent).  The `shortlist` entries of a list with the
+        largest relevance (ties to the lower id, then the lower position; None: min(256, max(k, 100))) are re-ranked: pick 1 is the
+        head; every later pick is the entry with the largest lam * relevance - (1 - lam) * max_sim, max_sim = its largest similarity
+        ("cosine" or "dot" over the item table: neighbors()' score, bit for bit) to the entries picked so far, among those whose id
+        is not picked yet; ties to the lower id, then the lower position.  Returns DiverseLists(ids, scores, values, max_sims,
+        positions) of [B, k] device tensors in pick order: scores = the picks' relevance, values / max_sims = the criterion and
+        max_sim at the pick (pick 1: lam * relevance and 0), positions = the index inside the row's list; padded with -1 / -inf / -inf /
+        -inf / -1.  lam = 1 gives the relevance order with ids deduplicated.  An id outside the table raises IndexError."""
+        eng = self.engine
+        dev = eng.device
+        who = "diversify"
+        if metric not in eng.NEIGHBOR_METRICS:
+            raise ValueError(f"metric must be one of {sorted(eng.NEIGHBOR_METRICS)}, got {metric!r}")
+        k, lam, shortlist = self._check_diversify(k, lam, shortlist, who)
+        if isinstance(candidates, (tuple, list)):
+            if len(candidates) != 2:
+                raise ValueError(f"{who}: candidates is a pair (items [n], offsets [B + 1]) or a [B, C] tensor")
+            B = int(torch.as_tensor(candidates[1]).numel()) - 1
+        else:
+            B = int(torch.as_tensor(candidates).shape[0])
+        if B < 1:
+            raise ValueError(f"{who}: no rows")
+        items, off, off_h = self._candidate_lists(candidates, B, who)
+        n = int(items.numel())
+        rel = torch.as_tensor(relevance).to(dev, torch.float32).reshape(-1).contiguous()
+        if rel.numel() != n:
+            raise ValueError(f"{who}: relevance must have one entry per candidate ({n}), got {rel.numel()}")
+        if eng.table_m is not None:
+            eng.flush_table()
+        out = DiverseLists(torch.empty(B, k, dtype=torch.int64, device=dev), torch.empty(B, k, dtype=torch.float32, device=dev),
+                           torch.empty(B, k, dtype=torch.float32, device=dev), torch.empty(B, k, dtype=torch.float32, device=dev),
+                           torch.empty(B, k, dtype=torch.int64, device=dev))
+        flags = eng.flags_holder()
+        eng.stream.wait_stream(torch.cuda.current_stream())
+        c0 = 0
+        while c0 < B:        # chunked on the host from the host's offsets, as _rank_lists: a row's picks depend on its own list only
+            c1 = min(B, c0 + self.DIVERSIFY_ROWS)
+            o0 = int(off_h[c0])
+            while c1 > c0 + 1 and int(off_h[c1]) - o0 > self.DIVERSIFY_CANDS:
+                c1 = c0 + max(1, (c1 - c0) // 2)
+            o1 = int(off_h[c1])
+            if o1 - o0 >= 2 ** 31 - 1:
+                raise ValueError(f"{who}: a list holds at most 2^31 - 2 candidates")
+            if c0 == 0 and c1 == B:
+                off_c = off
+            else:
+                with torch.cuda.stream(eng.stream):          # (the chunk's offsets count from its first candidate)
+                    off_c = off[c0:c1 + 1] - o0
+            eng.enqueue_mmr_lists(items[o0:o1], off_c, rel[o0:o1], o1 - o0, metric, lam, k, shortlist, *(t[c0:c1] for t in out), flags.err)
+            c0 = c1
+        torch.cuda.current_stream().wait_stream(eng.stream)
+        eng.check_index_error(flags)
+        return out
+
+    @torch.no_grad()
+    def recommend_diverse(self, seq_d1, seq_d2, domain_id, k: int = 10, lam: float = 0.7, metric: str = "cosine", shortlist=None, pool=None,
+                          exclude_history: bool = False) -> "DiverseLists":
+        """recommend(seq_d1, seq_d2, domain_id, k=shortlist, pool, exclude_history) followed by diversify(k, lam, metric, shortlist) over
+        each row's shortlist: that composition, bit for bit (positions: the rank in recommend()'s list; a row whose pool gave fewer than
+        `shortlist` items is diversified over what it has).  Comp models need exactly bs rows, as for recommend()."""
+        k, lam, shortlist = self._check_diversify(k, lam, shortlist, "recommend_diverse")
+        ids, scores = self.recommend(seq_d1, seq_d2, domain_id, k=shortlist, pool=pool, exclude_history=exclude_history)
+        return self.diversify_ranked(ids, scores, k=k, lam=lam, metric=metric)
+
+    def diversify_ranked(self, ids, scores, k: int = 10, lam: float = 0.7, metric: str = "cosine") -> "DiverseLists":
+        """diversify() over top-K results as recommend() and recommend_all() return them (ids / scores [B, M], M <= 256, padded with
+        -1 / -inf at the end of a row): every row's M entries are its shortlist, the padding is left out."""
+        M = int(ids.shape[1])
+        some = ids >= 0
+        if bool(some.all()):
+            return self.diversify(ids, scores, k=k, lam=lam, metric=metric, shortlist=M)
+        off = torch.zeros(ids.shape[0] + 1, dtype=torch.int64, device=ids.device)
+        off[1:] = torch.cumsum(some.sum(1), 0)
+        return self.diversify((ids[some], off), scores[some], k=k, lam=lam, metric=metric, shortlist=M)
 
     def check_indices(self) -> None:
         """Raise IndexError if any batch since the last check carried an item id outside the table (nn.Embedding raises on the spot,

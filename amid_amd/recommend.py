@@ -38,6 +38,12 @@ Takes the model flags of ``train_sr.py`` (``--model --emb_dim --hid_dim --seq_le
     --exclude_history       with --candidates: leave the ids of the row's own-domain sequence (under --history full the held-out item
                             too) out of its top-K.  Off by default: the list is the caller's
     --list_scores           with --candidates: also write offsets [N + 1], list_items [n] and list_scores [n], every entry's score
+    --diversify LAMBDA      re-rank by greedy Maximal Marginal Relevance (SASRec.diversify; LAMBDA in 0 .. 1 weighs the relevance, --metric
+                            is the item-item similarity): in the default mode over each row's top --shortlist of the same path, with
+                            --candidates over each row's own list scored by the same path (--exclude_history leaves the history out,
+                            --vectors_in as above).  --out gains mmr [N, K] (the criterion at each pick) and max_sim [N, K]; items and
+                            scores keep their names, scores stays the relevance.  Not with --similar_items or --audience_of
+    --shortlist M           with --diversify: how many of the best entries are re-ranked, --topk .. 256 (default min(256, max(topk, 100)))
 
     python recommend.py --data_root /path/to/AMID -ds amazon -dm cloth_sport --overlap_ratio 0.75 --model sasrec --bs 256 \
         --seq_len 50 --emb_dim 128 --weights runs/seed0/best_d1.pt --topk 10 --out cloth_sport_top10.npz
@@ -45,6 +51,7 @@ Takes the model flags of ``train_sr.py`` (``--model --emb_dim --hid_dim --seq_le
     python recommend.py ... --weights runs/seed0/best_d1.pt --similar_items all --metric cosine --topk 20 --out cloth_sport_similar.npz
     python recommend.py ... --weights runs/seed0/best_d1.pt --audience_of all --exclude_holders --topk 100 --out cloth_sport_audiences.npz
     python recommend.py ... --weights runs/seed0/best_d1.pt --candidates retrieved.npz --exclude_history --topk 20 --out cloth_sport_reranked.npz
+    python recommend.py ... --weights runs/seed0/best_d1.pt --diversify 0.7 --shortlist 100 --topk 10 --out cloth_sport_diverse10.npz
 
 Every row of the CSV gets a recommendation: the last batch is filled with rows from the start of the CSV (comp models need whole
 ``--bs``-row batches) and the surplus is cut off.  The ranking is ``SASRec.recommend_all``: one graph replay a batch.
@@ -82,7 +89,32 @@ def build_parser():
     p.add_argument("--candidates", type=str, default=None, help="FILE.npz (offsets, items) or text, a line a row: rank each row's own list to --out instead")
     p.add_argument("--exclude_history", action="store_true", help="--candidates: leave the row's own-domain history out of its top-K")
     p.add_argument("--list_scores", action="store_true", help="--candidates: also write the score of every entry of every list")
+    p.add_argument("--diversify", type=float, default=None, metavar="LAMBDA",
+                   help="re-rank by greedy MMR with this weight of the relevance, 0 .. 1 (top-K and --candidates; --metric is the similarity)")
+    p.add_argument("--shortlist", type=int, default=None, metavar="M", help="--diversify: the best M entries are re-ranked (--topk .. 256)")
     return p
+
+
+def check_diversify(args) -> None:
+    """--diversify / --shortlist against the other flags: SystemExit before anything is loaded or written."""
+    if args.diversify is None:
+        if args.shortlist is not None:
+            raise SystemExit("--shortlist belongs to --diversify")
+        return
+    if args.similar_items or args.audience_of:
+        raise SystemExit("--diversify re-ranks recommendations (top-K or --candidates): not with --similar_items or --audience_of")
+    if not 0.0 <= args.diversify <= 1.0:
+        raise SystemExit(f"--diversify must be in 0..1, got {args.diversify}")
+    if args.shortlist is not None and not args.topk <= args.shortlist <= 256:
+        raise SystemExit(f"--shortlist must be in --topk..256 ({args.topk}..256), got {args.shortlist}")
+    if args.shortlist is None:
+        args.shortlist = min(256, max(args.topk, 100))
+
+
+def diverse_fields(res) -> dict:
+    """DiverseLists -> the arrays --diversify writes: items, scores (the relevance), mmr, max_sim [N, K]."""
+    return {"items": res.ids.cpu().numpy(), "scores": res.scores.cpu().numpy(), "mmr": res.values.cpu().numpy(),
+            "max_sim": res.max_sims.cpu().numpy()}
 
 
 def full_history(seq_d1: np.ndarray, seq_d2: np.ndarray, i_node: np.ndarray, domain_id: np.ndarray):
@@ -215,16 +247,32 @@ def candidates_main(model, args, ds, vectors, history) -> dict:
     dev = torch.device(args.device)
     N = len(ds)
     items, offsets = candidate_lists(args.candidates, N, ds.user_nodes)
-    res = model.rank_candidates_from_vectors(vectors, torch.from_numpy(ds.domain_id).to(dev),
-                                             (torch.from_numpy(items).to(dev), torch.from_numpy(offsets)), k=args.topk, history=history,
-                                             list_scores=args.list_scores)
-    out = {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy(), "items": res.ids.cpu().numpy(),
-           "scores": res.scores.cpu().numpy(), "positions": res.positions.cpu().numpy()}
+    lists = (torch.from_numpy(items).to(dev), torch.from_numpy(offsets))
+    out = {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy()}
+    if args.diversify is None:
+        res = model.rank_candidates_from_vectors(vectors, torch.from_numpy(ds.domain_id).to(dev), lists, k=args.topk, history=history,
+                                                 list_scores=args.list_scores)
+        out.update(items=res.ids.cpu().numpy(), scores=res.scores.cpu().numpy())
+    else:
+        # every entry's score from the same path, then MMR over each list; an entry of the row's history is absent (NaN relevance)
+        scored = model.rank_candidates_from_vectors(vectors, torch.from_numpy(ds.domain_id).to(dev), lists, k=None, list_scores=True)
+        rel = scored.list_scores
+        if history is not None:
+            rel = rel.clone()
+            row = torch.repeat_interleave(torch.arange(N, device=dev), torch.from_numpy(np.diff(offsets)).to(dev))
+            for e0 in range(0, items.size, 1 << 18):
+                e = slice(e0, e0 + (1 << 18))
+                rel[e] = torch.where((history[row[e]] == lists[0][e].unsqueeze(1)).any(1), torch.full_like(rel[e], float("nan")), rel[e])
+        res = model.diversify(lists, rel, k=args.topk, lam=args.diversify, metric=args.metric, shortlist=args.shortlist)
+        out.update(diverse_fields(res))
+        res = scored._replace(positions=res.positions)
+    out["positions"] = res.positions.cpu().numpy()
     if args.list_scores:
         out.update(offsets=offsets, list_items=items, list_scores=res.list_scores.cpu().numpy())
     write_npz(args.out, out)
     print(f"wrote {args.out}: top-{args.topk} of the own lists of {N} rows ({items.size} candidates)"
-          + (", histories left out" if args.exclude_history else ""))
+          + (", histories left out" if args.exclude_history else "")
+          + (f", diversified (lambda {args.diversify}, {args.metric}) over the best {args.shortlist}" if args.diversify is not None else ""))
     return out
 
 
@@ -283,7 +331,8 @@ def main(argv=None):
         raise SystemExit("--vectors_in belongs to --audience_of or --candidates")
     if (args.exclude_history or args.list_scores) and not args.candidates:
         raise SystemExit("--exclude_history and --list_scores belong to --candidates")
-    cls = {"gru4rec": GRU4Rec, "sasrec": SASRec, "bert4rec": BERT4Rec}.get(args.model.lower())
+    check_diversify(args)
+    cls ={"gru4rec": GRU4Rec, "sasrec": SASRec, "bert4rec": BERT4Rec}.get(args.model.lower())
     if cls is None:
         raise SystemExit(f"unknown --model {args.model!r} (gru4rec | sasrec | bert4rec)")
     if cls is GRU4Rec and (args.isInC or args.isItC or args.isDR):
@@ -342,13 +391,19 @@ def main(argv=None):
         if vectors is not None:
             out["vectors"] = vectors
         return out
-    ids, scores = model.recommend_all(users, k=args.topk, pool=pool, exclude_history=True, use_graph=not args.no_graph)
-    out = {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy(),
-           "items": ids.reshape(-1, args.topk)[:N].cpu().numpy(), "scores": scores.reshape(-1, args.topk)[:N].cpu().numpy()}
+    kk = args.topk if args.diversify is None else args.shortlist       # (--diversify: the shortlist is the top-M of the same path)
+    ids, scores = model.recommend_all(users, k=kk, pool=pool, exclude_history=True, use_graph=not args.no_graph)
+    out = {"user_id": ds.user_nodes.copy(), "domain_id": ds.domain_id.copy()}
+    if args.diversify is None:
+        out.update(items=ids.reshape(-1, kk)[:N].cpu().numpy(), scores=scores.reshape(-1, kk)[:N].cpu().numpy())
+    else:
+        out.update(diverse_fields(model.diversify_ranked(ids.reshape(-1, kk)[:N], scores.reshape(-1, kk)[:N], k=args.topk, lam=args.diversify,
+                                                         metric=args.metric)))
     if os.path.dirname(args.out):
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
     np.savez(args.out, **out)
-    print(f"wrote {args.out}: top-{args.topk} of {N} rows ({sel.shape[0]} batches of {args.bs})")
+    print(f"wrote {args.out}: top-{args.topk} of {N} rows ({sel.shape[0]} batches of {args.bs})"
+          + (f", diversified (lambda {args.diversify}, {args.metric}) over the top {kk}" if args.diversify is not None else ""))
     if vectors is not None:
         out["vectors"] = vectors
     out["metrics"] = None

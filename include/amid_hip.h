@@ -1231,6 +1231,31 @@ int amid_rank_lists_f32(const float* u, long long u_dom_stride, const long long*
                         int hid, int k, void* workspace, int* flags, float* list_scores, long long* ids, float* scores,
                         long long* positions, void* stream);
 
+/* ---- diversified top-K: greedy MMR over each row's own list (csrc/diversify.hip) -------------------------------------------------------------------
+ * B rows, each with a list of its own as in amid_rank_lists_f32: row b's list is cand[cand_off[b] .. cand_off[b + 1]) (int64 ids of table
+ * [n_rows, D] rows, duplicates allowed, lists may be empty) with a relevance rel[j] per entry; cand_off [B + 1] int64 on the device, n_cand
+ * the host's copy of cand_off[B]; offsets are clamped into [0, n_cand] on the device as there (same flag, same behaviour of offsets that do
+ * not rise).  cand and rel may be null when n_cand is 0.
+ * An entry is absent if its id lies outside [0, n_rows) (that also raises AMID_FLAG_INDEX_RANGE in *flags; never dereferenced) or its rel is
+ * NaN (what amid_rank_lists_f32 writes into list_scores for such ids).  The shortlist is the `shortlist` best present entries: larger rel
+ * first, ties to the lower id, further ties to the lower position -- amid_rank_lists_f32's order, independent of how a list is cut into
+ * tiles.  Pick 1 is its head (value = lambda * rel, max_sim = 0).  Pick j >= 2: among the shortlist entries not picked whose id differs
+ * from every picked id, the largest v(c) = (lambda * rel(c)) - ((1 - lambda) * m(c)), m(c) = the running fmaxf over the picked s of
+ * sim(c, s); fp32, no contraction, 1 - lambda formed once; ties to the lower id, then the lower position; an entry whose v is NaN is never
+ * picked.  It stops at K picks or when nothing remains.  sim(c, s) is amid_neighbors_f32's score of candidate row s for query row c under
+ * the same metric (0 dot, 1 cosine), bit for bit.
+ * out_ids / out_rel / out_value / out_max_sim / out_positions [B, K] (all but out_ids may be null): the picks in pick order -- the id, the
+ * entry's rel, v and m at the pick, the entry's index inside its own list; padding -1 / -inf / -inf / -inf / -1.
+ * 1 <= K <= shortlist <= 256, metric 0 / 1, lambda in [0, 1] (a NaN is refused), null cand_off, table, ws, flags or out_ids, cand or rel null
+ * with n_cand > 0, B <= 0, n_cand < 0 or >= 2^31 - 1, n_rows <= 0: AMID_ERR_ARG; D other than 64 / 128: AMID_ERR_UNSUPPORTED; both before
+ * any device call.  Three launches (the prefix of the rows' unit counts; the units' shortlists; per row the merge and the greedy rounds) on
+ * the stream only, no host read, no allocation, no float atomics; it can be captured in a graph.
+ * ws: amid_mmr_workspace_bytes(B, n_cand, D, K, shortlist) bytes (negative: bad sizes or D; non-decreasing in every argument). */
+long long amid_mmr_workspace_bytes(int B, long long n_cand, int D, int K, int shortlist);
+int amid_mmr_lists_f32(const long long* cand, const long long* cand_off, const float* rel, long long n_cand, int B, const float* table,
+                       long long n_rows, int D, int metric, float lambda, int K, int shortlist, void* ws, int* flags, long long* out_ids,
+                       float* out_rel, float* out_value, float* out_max_sim, long long* out_positions, void* stream);
+
 /* ---- BERT4Rec strips on bf16 pieces (round 5; csrc/bert_strip.hip MODE 3) ------------------------------------------------------------------
  * The strip launches of a TransformerBlock (model_seq.py:242-245 and its autograd) with every product as six bf16 piece pairs at fp32
  * accuracy -- what SASRec's strips run on since round 4.  Each 128 x 128 weight TILE a chain multiplies with is a three-plane fragment image
