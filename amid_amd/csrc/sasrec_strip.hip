@@ -21,6 +21,7 @@
 #include "attention_mfma.h"
 #include "seq_bwd.h"
 #include "scorer_sum.h"
+#include "strip_px.h"
 #include <type_traits>
 
 namespace amid {
@@ -704,7 +705,10 @@ extern "C" int amid_sas_strip_oproj_ffn_fwd_infer_f32(const float* o, const floa
 struct StripBwdLaunch {
     int B = 0, T = 0, D = 0; const int* live = nullptr;
     const void* sort_plan = nullptr; int sort_phase = 0;
-    int mma_bf16 = 0;                    // 0: fp32 products, 1: operands rounded to bf16, 3: three bf16 pieces (D 128)
+    int mma_bf16 = 0;                    // 0: fp32 products, 1: operands rounded to bf16, 3: three bf16 pieces (D 128),
+                                         // 4: three pieces, the N-split build (sasrec_strip_px.hip; D 128, dropout p = 0.5 or none)
+    const float* ln_stat = nullptr;      // mma_bf16 = 4: the forward's row statistics of the launch's (first) chain's layer, or NULL
+    const float* f_ln_stat = nullptr;    // ... of the fused feed-forward chain's layer, or NULL
     void* stream = nullptr;
 };
 #define STRIP_BWD_LAUNCH(l) StripBwdLaunch l; l.B = B; l.T = T; l.D = D; l.live = live; l.mma_bf16 = mma_bf16; l.stream = stream
@@ -728,6 +732,7 @@ static int strip_ffn_bwd(const FfnBwdCall& c, const StripBwdLaunch& l) {
     SortRider rd;
     if (int e = make_rider(rd, l.sort_plan, l.sort_phase)) return e;
     if (rd.phase != 0 && rd.phase != 2) return AMID_ERR_UNSUPPORTED;           // this launch carries phase 2
+    if (D == 128 && mma_bf16 == 4) return launch_ffn_bwd_px(a, l.ln_stat, sg, rd, l.stream);
     if (D == 128) return mma_bf16 == 3 ? launch_ffn_bwd<128, 3>(sg, rd, l.stream, a) : mma_bf16 ? launch_ffn_bwd<128, 1>(sg, rd, l.stream, a)
                                                                                           : launch_ffn_bwd<128, 0>(sg, rd, l.stream, a);
     if (D == 64) return launch_ffn_bwd<64, 0>(sg, rd, l.stream, a);
@@ -808,10 +813,11 @@ static int strip_qkv_bwd(const StripQkvBwdCall& c, const StripBwdLaunch& l) {
     if (rd.phase != 0 && rd.phase != (ffn ? 3 : 4)) return AMID_ERR_UNSUPPORTED;      // phase 3 with the fused feed-forward backward, 4 without
     ScorerSum ss = {};
     if (c.scorer != nullptr) {
-        if (!(ffn && D == 128 && (mma_bf16 == 3 || mma_bf16 == 1))) return AMID_ERR_UNSUPPORTED;       // the riders' host: the middle launch on bf16 pieces / one piece (with or without a sort rider)
+        if (!(ffn && D == 128 && (mma_bf16 == 3 || mma_bf16 == 1 || mma_bf16 == 4))) return AMID_ERR_UNSUPPORTED;       // the riders' host: the middle launch on bf16 pieces / one piece (with or without a sort rider)
         ss = *c.scorer;
     }
     void* const st = l.stream;
+    if (D == 128 && mma_bf16 == 4) return launch_qkv_bwd_px(a, f, ffn, l.ln_stat, l.f_ln_stat, ss, sg, rd, st);
     if (D == 128 && mma_bf16 == 3) return ffn ? launch_qkv_bwd<128, true, 3>(sg, rd, st, a, f, ss) : launch_qkv_bwd<128, false, 3>(sg, rd, st, a, f, ss);
     if (D == 128 && mma_bf16) return ffn ? launch_qkv_bwd<128, true, 1>(sg, rd, st, a, f, ss) : launch_qkv_bwd<128, false, 1>(sg, rd, st, a, f, ss);
     if (D == 128) return ffn ? launch_qkv_bwd<128, true, 0>(sg, rd, st, a, f, ss) : launch_qkv_bwd<128, false, 0>(sg, rd, st, a, f, ss);
@@ -894,6 +900,34 @@ extern "C" int amid_sas_strip_qkv_bwd_emb_f32(const float* dq, const float* dk, 
                                               float emb_p_drop, const void* sort_plan, int sort_phase, int mma_bf16, void* stream) {
     AMID_CHECK_ARG(emb_tmq != nullptr && dx != nullptr);
     STRIP_QKV_BWD_CALL(c); c.dx = dx; c.emb_tmq = emb_tmq; c.emb_p_drop = emb_p_drop; STRIP_BWD_LAUNCH(l); STRIP_BWD_RIDER(l);
+    return strip_qkv_bwd(c, l);
+}
+
+// The N-split build of the q / k / v backward launches (mma_bf16 = 4 of the entries above; csrc/sasrec_strip_px.hip) with everything a launch
+// can carry named in one call: the fused feed-forward backward (fh != NULL; dx is then not written), or the embedding backward (emb_tmq !=
+// NULL), the forward's row statistics (ln_stat: the q / k / v chain's layer, LN1's mean and rstd at +0; f_ln_stat: the fused chain's layer,
+// LN2's at +2; NULL: taken from the rows), a sort rider (sort_plan != NULL: phase 3 with the fused chain, 4 without) and the scorer sums
+// (hidg != NULL; with the fused chain only).  The weights are three-plane images of the transposes.  D = 128, dropout 0.5 or none.
+extern "C" int amid_sas_strip_qkv_bwd_px_f32(const float* dq, const float* dk, const float* dv, const float* dr, const float* x,
+                                             const float* const* ln_w, const float* const* wqT, const float* const* wkT, const float* const* wvT,
+                                             float ln_eps, int B, int T, int D, const int* live, float* dx, float* ln_part,
+                                             const unsigned char* tmq, const float* fh, const float* fr, const float* const* fln_w,
+                                             const float* const* fw1T, const float* const* fw2T, const float* const* fwoT, int flayer,
+                                             const void* step_state, int train, float p_drop, float* fdpre2, float* fdpre1, float* fdr,
+                                             float* fd_o, float* fln_part, const unsigned char* emb_tmq, float emb_p_drop, const float* ln_stat,
+                                             const float* f_ln_stat, const void* sort_plan, int sort_phase, const float* hidg, const float* u,
+                                             const float* items, int NI, int hid, float* dW1, float* db1, float* dW2, float* db2, void* stream) {
+    if (D != 128) return AMID_ERR_UNSUPPORTED;
+    const int mma_bf16 = 4;
+    ScorerSum ss = {};
+    if (hidg != nullptr) {
+        AMID_CHECK_ARG(fh != nullptr && u && items && NI > 0 && hid > 0 && dW1 && db1 && dW2 && db2);
+        AMID_CHECK_ARG(((((unsigned long long)dW1) | ((unsigned long long)u) | ((unsigned long long)items)) & 15) == 0);
+        ss = scorer_sum_args(hidg, u, items, B, NI, D, hid, dW1, db1, dW2, db2);
+    }
+    STRIP_QKV_BWD_CALL(c); STRIP_QKV_BWD_FFN(c); c.dx = dx; c.emb_tmq = emb_tmq; c.emb_p_drop = emb_p_drop;
+    if (hidg != nullptr) c.scorer = &ss;
+    STRIP_BWD_LAUNCH(l); STRIP_BWD_RIDER(l); l.ln_stat = ln_stat; l.f_ln_stat = f_ln_stat;
     return strip_qkv_bwd(c, l);
 }
 #undef AMID_FFN_BWD_CALL

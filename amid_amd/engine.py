@@ -303,6 +303,15 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
     # six piece pairs: csrc/strip_gemm.h strip_mma16x6, strip_chain.h RingP3), from three-plane images of the TRANSPOSED weights; "0": fp32
     # matrix instructions
     BWD_SPLIT = True
+    # ... in the N-split build (csrc/sasrec_strip_px.hip: eight waves per 64-row tile, two per SIMD, each owning half the output columns; the
+    # entry points' products mode 4) wherever the strips run on three pieces: D 128, dropout 0.5 -- whatever the fold switches say.  One bit
+    # per launch, top down: 1 = layer 1's feed-forward chain, 2 = layer 1's q / k / v chain + layer 0's feed-forward chain, 4 = layer 0's
+    # q / k / v chain (+ the embedding backward); 0: the strip build everywhere (`bench.py --set STRIP_NSPLIT=0`, profiles/strip_nsplit.md)
+    STRIP_NSPLIT = 7
+
+    def _strip_mode(self, bf: int, launch: int) -> int:
+        """The products mode of backward strip launch `launch` (0, 1, 2 top down) of a step whose strips take mode `bf`."""
+        return 4 if bf == 3 and self.D == 128 and SASREC_P_DROP == 0.5 and (int(self.STRIP_NSPLIT) >> launch) & 1 else bf
 
     # ------------------------------------------------------------------ launch sequences
     def enqueue_prepare(self, pl: SasrecPlan, sparse: bool, bump_step: bool = False, defer_sort: bool = False) -> None:
@@ -1142,7 +1151,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             ride = lambda ph: (plan_addr, ph) if riding else ()      # noqa: E731
             L.call(f"amid_sas_strip_ffn_bwd{sfx}_f32", pl.dxbuf.data_ptr(), tm, h1, r1, lnw1, w1T1, w2T1, woT1, SASREC_LN_EPS, B, T, D, lv, 1, st, tr,
                    SASREC_P_DROP, pl.dpre2[1].data_ptr(), pl.dpre1[1].data_ptr(), pl.dr[1].data_ptr(), pl.d_o.data_ptr(), ln2p[1].data_ptr(),
-                   *ride(2), bf, s)
+                   *ride(2), self._strip_mode(bf, 0), s)
             attn_bwd(1)
             # layer 1's q / k / v + LayerNorm1 backward and layer 0's feed-forward / out-projection backward: one launch
             if t2:      # ... whose idle CUs also sum the scorer's weight gradients from the head's per-sample hidden gradients
@@ -1154,23 +1163,23 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
                              wvT=self._wT(1, 2), ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, live=lv, ln_part=ln1p[1].data_ptr(), tmq=tm, fh=h0, fr=r0,
                              fln_w=lnw0, fw1T=w1T0, fw2T=w2T0, fwoT=woT0, flayer=0, step_state=st, train=tr, p_drop=SASREC_P_DROP,
                              fdpre2=pl.dpre2[0].data_ptr(), fdpre1=pl.dpre1[0].data_ptr(), fdr=pl.dr[0].data_ptr(), fd_o=pl.d_o.data_ptr(),
-                             fln_part=ln2p[0].data_ptr(), mma_bf16=bf, hidg=self._hidg(pl).data_ptr(),
+                             fln_part=ln2p[0].data_ptr(), mma_bf16=self._strip_mode(bf, 1), hidg=self._hidg(pl).data_ptr(),
                              u=pl.u.data_ptr(), items=items, NI=NI, hid=self.hid, stream=s)
             else:
                 L.call(f"amid_sas_strip_qkv_bwd{sfx}_f32", pl.dq_l[1].data_ptr(), pl.dk_l[1].data_ptr(), pl.dv_l[1].data_ptr(), pl.dr[1].data_ptr(),
                        pl.x[1].data_ptr(), self._pp("sac{d}.attention_layernorms.1.weight"), self._wT(1, 0), self._wT(1, 1), self._wT(1, 2),
                        SASREC_LN_EPS, B, T, D, lv, None, ln1p[1].data_ptr(), tm, h0, r0, lnw0, w1T0, w2T0, woT0, 0, st, tr, SASREC_P_DROP,
-                       pl.dpre2[0].data_ptr(), pl.dpre1[0].data_ptr(), pl.dr[0].data_ptr(), pl.d_o.data_ptr(), ln2p[0].data_ptr(), *ride(3), bf, s)
+                       pl.dpre2[0].data_ptr(), pl.dpre1[0].data_ptr(), pl.dr[0].data_ptr(), pl.d_o.data_ptr(), ln2p[0].data_ptr(), *ride(3), self._strip_mode(bf, 1), s)
             attn_bwd(0)
             if t2:      # ... with the embedding layer's backward applied on the strip (no amid_embed_bwd launch)
                 L.call("amid_sas_strip_qkv_bwd_emb_f32", pl.dq_l[0].data_ptr(), pl.dk_l[0].data_ptr(), pl.dv_l[0].data_ptr(), pl.dr[0].data_ptr(),
                        pl.x[0].data_ptr(), self._pp("sac{d}.attention_layernorms.0.weight"), self._wT(0, 0), self._wT(0, 1), self._wT(0, 2),
-                       SASREC_LN_EPS, B, T, D, lv, dx_in, ln1p[0].data_ptr(), pl.tmq.data_ptr(), st, tr, SASREC_P_DROP, plan_addr, 4 if riding else 0, bf, s)
+                       SASREC_LN_EPS, B, T, D, lv, dx_in, ln1p[0].data_ptr(), pl.tmq.data_ptr(), st, tr, SASREC_P_DROP, plan_addr, 4 if riding else 0, self._strip_mode(bf, 2), s)
             else:
                 L.call(f"amid_sas_strip_qkv_bwd{sfx}_f32", pl.dq_l[0].data_ptr(), pl.dk_l[0].data_ptr(), pl.dv_l[0].data_ptr(), pl.dr[0].data_ptr(),
                        pl.x[0].data_ptr(), self._pp("sac{d}.attention_layernorms.0.weight"), self._wT(0, 0), self._wT(0, 1), self._wT(0, 2),
                        SASREC_LN_EPS, B, T, D, lv, dx_in, ln1p[0].data_ptr(), None, None, None, None, None, None, None, 0, None, 0, 0.0, None,
-                       None, None, None, None, *ride(4), bf, s)
+                       None, None, None, None, *ride(4), self._strip_mode(bf, 2), s)
         else:
             rows, suf, rpt = ("_rows", pl.rt_suffix_v, pl.rpt_v) if live else ("", pl.rt_suffix, pl.rpt)
             ln1p, ln2p = (pl.ln1_part_v, pl.ln2_part_v) if live else (pl.ln1_part, pl.ln2_part)

@@ -880,13 +880,32 @@ int amid_sas_strip_qkv_bwd_emb_f32(const float* dq, const float* dk, const float
  * 64-row tile -- four strips x two column parts --, the chain's operands cross the parts through LDS as bf16 pieces, the three-plane images of
  * the TRANSPOSED weights stream through three plane slots (the forward's machinery, amid_sas_seq_fwd_split_f32).  w1T / w2T / woT: per domain,
  * the images ([3][D][D] bf16).  ln_stat: the forward's row statistics of the layer ([2 B T][4], LN2's mean and rstd at +2) or NULL.
- * sort_plan: optional rider (phase 2).  D = 128, p_drop = 0.5 or eval.  Agrees with the strip build to rounding (the LayerNorm backward's row
- * sums are added part by part). */
+ * sort_plan: optional rider (phase 2).  D = 128, p_drop = 0.5 or eval.  Gives the strip build's bits with ln_stat = NULL (the same operations in
+ * the same order); with the forward's statistics the agreement is to rounding. */
 int amid_sas_strip_ffn_bwd_px_f32(const float* dxo, const unsigned char* tmq, const float* h, const float* r, const float* const* ln_w,
                                   const float* const* w1T, const float* const* w2T, const float* const* woT, float ln_eps, int B, int T, int D,
                                   const int* live, int layer, const void* step_state, int train, float p_drop, float* dpre2, float* dpre1,
                                   float* dr, float* d_o, float* ln_part, const float* ln_stat, const void* sort_plan, int sort_phase,
                                   void* stream);
+/* mma_bf16 = 4 of the backward strip entry points (amid_sas_strip_ffn_bwd(_sort)_f32, amid_sas_strip_qkv_bwd(_sort)(_scorer)_f32,
+ * amid_sas_strip_qkv_bwd_scorer_f32, amid_sas_strip_qkv_bwd_emb_f32): the operands of mma_bf16 = 3 (three-plane images of the transposes)
+ * through the N-split build above -- the same tensors written, the same riders carried (sort phases 2 / 3 / 4 on a rider workgroup's first
+ * four waves, the scorer sums behind or in front of the tiles) and the SAME BITS as mma_bf16 = 3: the build performs the strip build's
+ * operations in its order.  D = 128, every dropout rate 0.5 (or eval): AMID_ERR_UNSUPPORTED otherwise.  Those entries pass no row
+ * statistics (they are taken from the rows; with the forward's statistics -- the _px_ entries -- the agreement is to rounding).
+ * amid_sas_strip_qkv_bwd_px_f32: the q / k / v launches of that build with everything they can carry named in one call -- the fused
+ * feed-forward backward of the layer below (fh != NULL: dx is not written) or the embedding backward (emb_tmq != NULL), the forward's row
+ * statistics ([2 B T][4]; ln_stat: the q / k / v chain's layer, LN1's mean and rstd at +0; f_ln_stat: the fused chain's layer, LN2's at +2;
+ * NULL: taken from the rows), a sort rider (sort_plan != NULL: phase 3 with the fused chain, 4 without) and the scorer sums (hidg != NULL,
+ * with the fused chain only; the operands of amid_sas_strip_qkv_bwd_scorer_f32). */
+int amid_sas_strip_qkv_bwd_px_f32(const float* dq, const float* dk, const float* dv, const float* dr, const float* x, const float* const* ln_w,
+                                  const float* const* wqT, const float* const* wkT, const float* const* wvT, float ln_eps, int B, int T, int D,
+                                  const int* live, float* dx, float* ln_part, const unsigned char* tmq, const float* fh, const float* fr,
+                                  const float* const* fln_w, const float* const* fw1T, const float* const* fw2T, const float* const* fwoT,
+                                  int flayer, const void* step_state, int train, float p_drop, float* fdpre2, float* fdpre1, float* fdr,
+                                  float* fd_o, float* fln_part, const unsigned char* emb_tmq, float emb_p_drop, const float* ln_stat,
+                                  const float* f_ln_stat, const void* sort_plan, int sort_phase, const float* hidg, const float* u,
+                                  const float* items, int NI, int hid, float* dW1, float* db1, float* dW2, float* db2, void* stream);
 /* amid_sas_wgrad_rows_f32 (mma_bf16 = 3, D = 128) carrying the LAST phase (5: run heads) of a sort plan as extra workgroups.
  * (amid_sas_wgrad_rows_sort_ln_f32 also takes mma_bf16 = 4: the same launch staging and multiplying ONE bf16 piece per operand -- bf16
  * products with fp32 accumulation, the folded bf16 step's weight gradients; round 6) */
