@@ -452,7 +452,14 @@ int amid_scorer_multi_fwd_bwd_f32(const float* u, const float* items, const floa
  *               x0[g,b,0..2T) = [e[g,b,:] | Z[g]] + P_g[0..2T), dropout, (==0) mask (:470, :361-366); tmq as amid_embed_fwd_f32
  *   bwd       : after amid_embed_bwd_f32(dx0, tmq, B, 2T, ...) -- whose pos_emb partials of rows T..2T-1 are dZ's partials --:
  *               InnerComp parameter gradients (written whole) and dxg[g,j,t] = dx0[g,j,t] + w_bs_g[j] gate_j (dZ[g][t] W_nn_g).
- * xg: [2, B, T, D] plain gathered rows (amid_gather_rows_f32); host pointer arrays hold 2 device pointers (inc_d1, inc_d2). */
+ * xg: [2, B, T, D] plain gathered rows (amid_gather_rows_f32); host pointer arrays hold 2 device pointers (inc_d1, inc_d2).
+ * Limits (tests/test_gpu_innercomp.py holds each entry to float64 on both sides of them; every refusal comes before anything touches a
+ * device, no output is written):
+ *   score          : D % 4 == 0 (AMID_ERR_ARG otherwise); a row's T gathered rows, padded by 4 floats, in LDS: T (D + 4) 4 <= 160 KiB - 256
+ *                    bytes (T <= 309 at D 128), AMID_ERR_UNSUPPORTED beyond
+ *   embed_fwd, bwd : D % 4 == 0 and D <= 256 (AMID_ERR_ARG otherwise); the forward keeps the batch's gated weights, eight row groups'
+ *                    partial sums and S[t] in LDS: ((B + 3) & ~3) + 9 D <= 16384 floats (B <= 15232 at D 128), AMID_ERR_UNSUPPORTED beyond.
+ *                    The backward has no limit on B. */
 int amid_inc_score_f32(const float* xg, int B, int T, int D, float* s, void* stream);
 int amid_inc_embed_fwd_f32(const float* xg, const float* s, const float* const* w_nn, const float* const* b_nn,
                            const float* const* w_bs, const float* const* b_bs, float threshold, const float* pos0,
@@ -466,7 +473,10 @@ int amid_inc_bwd_f32(const float* dpos_part, int nsplit, const float* xg, const 
  * model_seq.py:457): s_all [2, Bg] = the ranks' amid_inc_score_f32 outputs all-gathered per domain.  phase 1: gates, this shard's partial S
  * [2, T, D], sw; the caller all-reduces S; phase 2: Z and the encoder input.  Backward: phase 1 = this shard's dZ [2, T, D]; the caller
  * all-reduces it; phase 2 = dS, the parameter gradients (W_nn, b_nn, b_bs times gscale = 1 / world: every rank computes them alike and
- * the dense exchange sums the ranks; w_bs: this shard's slice, zeros elsewhere) and the table-row gradients */
+ * the dense exchange sums the ranks; w_bs: this shard's slice, zeros elsewhere) and the table-row gradients.
+ * phase is 1 or 2 and 0 <= j0, j0 + B <= Bg (AMID_ERR_ARG otherwise); the shards need not be equal (129 + 128 rows of 257 are held to
+ * float64 like equal ones); w_bs and dw_bs span Bg; limits otherwise as above, with the LDS bound on the shard's own B.  With one shard
+ * (Bg = B, j0 = 0) phases 1 and 2 write bit for bit what the unsharded entry writes. */
 int amid_inc_embed_fwd_shard_f32(const float* xg, const float* s_all, const float* const* w_nn, const float* const* b_nn,
                                  const float* const* w_bs, const float* const* b_bs, float threshold, const float* pos0, const float* pos1,
                                  int B, int T, int D, int Bg, int j0, int phase, float* gate, float* S, float* Z, float* sw, float* x0,
@@ -484,7 +494,11 @@ int amid_inc_bwd_shard_f32(const float* dpos_part, int nsplit, const float* xg, 
  *   score : s [2, B];   fwd : gate, S, Z, sw as amid_inc_embed_fwd_f32 and x0[g,b,0..2T) = [e[g,b,:] | Z[g]]
  *   bwd   : dZ[g][t] = sum_b dx0[g,b,T+t] (fixed order), the modules' parameter gradients (written whole) and
  *           dxg[sd,j,t] = dx0[sd,j,t] + w_bs_g[j] gate_g[j] (dZ[g][t] W_nn_g),  sd = cross ? 1-g : g
- * amid_key_keep_tiled_u8: the key mask of :286 / :294, keep[b][r*T + t] = seq[b][t] > 0 for r < reps. */
+ * amid_key_keep_tiled_u8: the key mask of :286 / :294, keep[b][r*T + t] = seq[b][t] > 0 for r < reps.
+ * Limits as amid_inc_score_f32 / amid_inc_embed_fwd_f32 / amid_inc_bwd_f32 (D % 4 == 0; fwd, bwd: D <= 256, AMID_ERR_ARG; fwd:
+ * ((B + 3) & ~3) + 9 D <= 16384 floats of LDS, AMID_ERR_UNSUPPORTED); the score with cross = 1 holds both domains' rows:
+ * 2 T (D + 4) 4 <= 160 KiB - 256 bytes (T <= 154 at D 128), AMID_ERR_UNSUPPORTED beyond.  With cross = 0 the score is
+ * amid_inc_score_f32's bit for bit; with cross = 1, s[0] == s[1] bit for bit (the same products added in the same order). */
 int amid_bert_comp_score_f32(const float* xg, int B, int T, int D, int cross, float* s, void* stream);
 int amid_bert_comp_fwd_f32(const float* xg, const float* s, const float* const* w_nn, const float* const* b_nn,
                            const float* const* w_bs, const float* const* b_bs, float threshold, int cross, int B, int T, int D,
@@ -1306,7 +1320,8 @@ int amid_bert_seq_fwd_gather_infer_f32(float* x_out, const float* const* la1, co
                                        const long long* seq_d2, void* stream);
 /* BERT4Rec(isInC / isItC) under data parallel (round 5): amid_bert_comp_fwd_f32 / _bwd_f32 (model_seq.py:283-294 and its autograd) on a
  * shard of the global batch, cut at the all-reduces of the token sums S (forward) and of their gradient dZ (backward) exactly as
- * amid_inc_embed_fwd_shard_f32 / amid_inc_bwd_shard_f32: B rows = samples j0 .. j0 + B - 1 of Bg, s_all [2, Bg] the all-gathered scores. */
+ * amid_inc_embed_fwd_shard_f32 / amid_inc_bwd_shard_f32: B rows = samples j0 .. j0 + B - 1 of Bg, s_all [2, Bg] the all-gathered scores.
+ * Arguments and limits as there: phase 1 or 2, j0 + B <= Bg (AMID_ERR_ARG), unequal shards accepted. */
 int amid_bert_comp_fwd_shard_f32(const float* xg, const float* s_all, const float* const* w_nn, const float* const* b_nn,
                                  const float* const* w_bs, const float* const* b_bs, float threshold, int cross, int B, int T, int D, int Bg,
                                  int j0, int phase, float* gate, float* S, float* Z, float* sw, float* x0, void* stream);
