@@ -115,19 +115,62 @@ class DualDomainSeqDataset:
         return self
 
 
+def item_counts(ds: DualDomainSeqDataset, onto=None):
+    """Popularity of every pool entry -> two int64 arrays aligned with ds.pool[0] and ds.pool[1].  For domain g an id's count is its
+    occurrences among the non-pad entries of the tokenised seq_d{g+1} of all rows, plus the number of rows of domain g whose positive
+    (i_node) is that id.  Reads the arrays both the CSV constructor and from_tokenised fill.
+    onto=(pool_d1, pool_d2): the counts aligned with those pools instead (another dataset's), matched by id, 0 where ds never saw
+    the id -- how an evaluation loader gets the popularity of the training CSV."""
+    pools = ds.pool if onto is None else onto
+    if len(pools) != 2:
+        raise ValueError("onto must be a pair of pools (pool_d1, pool_d2)")
+    out = []
+    for g, seq in enumerate((ds.seq_d1, ds.seq_d2)):
+        ids = np.concatenate((seq[seq != ds.pad_id], ds.i_node[(ds.domain_id != 0) == bool(g)]))
+        seen, cnt = np.unique(ids, return_counts=True)
+        pool = np.asarray(pools[g], dtype=np.int64)
+        c = np.zeros(len(pool), dtype=np.int64)
+        if len(seen):
+            at = np.minimum(np.searchsorted(seen, pool), len(seen) - 1)
+            hit = seen[at] == pool
+            c[hit] = cnt[at[hit]]
+        out.append(c)
+    return out[0], out[1]
+
+
+def popularity_weights(counts, power: float):
+    """(w, cum) int64 for one pool: w = floor(counts ** power * 65536) + 1 (16 fractional bits; the + 1 keeps a never-seen id
+    drawable; power 0 makes every weight 65537, which is uniform) and cum = cumsum(w), inclusive; total = cum[-1].  0 <= power <= 1.
+    A total at or above 2**62 is a ValueError: the sampler's t = (r64 * total) >> 64 and its prefix compare stay inside int64."""
+    if not 0.0 <= power <= 1.0:
+        raise ValueError(f"power must be in 0..1, got {power}")
+    counts = np.asarray(counts)
+    if counts.ndim != 1 or len(counts) == 0 or (counts < 0).any():
+        raise ValueError("counts must be a non-empty 1-d array of non-negative numbers")
+    wf = np.floor(counts.astype(np.float64) ** power * 65536.0)
+    if not (wf < 2.0 ** 62).all() or sum(int(x) + 1 for x in wf.tolist()) >= 2 ** 62:
+        raise ValueError("popularity weights sum to 2**62 or more")
+    w = wf.astype(np.int64) + 1
+    return w, np.cumsum(w)
+
+
 class DeviceBatches:
     """DataLoader(batch_size, shuffle, drop_last=True) over a tokenised dataset resident on the device."""
 
     def __init__(self, ds: DualDomainSeqDataset, batch_size: int, shuffle: bool, device, seed: int = 0, rank: int = 0, world: int = 1,
-                 negatives: str = "device"):
+                 negatives: str = "device", counts=None, power: float = 1.0):
         """rank / world: data parallel -- every rank walks the same shuffled order (same seed) in global batches of
         world x batch_size rows and keeps its own contiguous slice (DistributedSampler-style, drop_last).
         negatives: "device" = drawn per epoch by amid_sample_negatives_i64; "fixture" = the draw stored with a tokenised fixture
-        (DualDomainSeqDataset.from_tokenised: what the reference's random.sample produced under random.seed(0); needs no GPU)."""
+        (DualDomainSeqDataset.from_tokenised: what the reference's random.sample produced under random.seed(0); needs no GPU);
+        "popularity" = drawn per epoch by amid_sample_negatives_weighted_i64 with weights popularity_weights(counts, power), counts a
+        pair aligned with ds.pool (None: item_counts(ds)); the weight prefixes are built here, once, and stay on the device."""
         self.ds, self.bs, self.shuffle, self.device = ds, batch_size, shuffle, torch.device(device)
         self.rank, self.world = rank, world
-        if negatives not in ("device", "fixture"):
-            raise ValueError(f"negatives must be 'device' or 'fixture', got {negatives!r}")
+        if negatives not in ("device", "fixture", "popularity"):
+            raise ValueError(f"negatives must be 'device', 'fixture' or 'popularity', got {negatives!r}")
+        if negatives != "popularity" and (counts is not None or power != 1.0):
+            raise ValueError("counts / power belong to negatives='popularity'")
         if negatives == "fixture" and (not hasattr(ds, "ref_neg") or ds.ref_neg.shape[1] < (1 if ds.isTrain else ds.neg_nums)):
             raise ValueError("negatives='fixture' needs a tokenised dataset carrying enough stored negatives")
         self.negatives = negatives
@@ -139,6 +182,12 @@ class DeviceBatches:
         self.gen = torch.Generator().manual_seed(seed)
         # negative sampling state on the device: the two item pools and every row's own items (dataset_seq.py:141-142, :188/:206)
         self.pool = [to(p) for p in ds.pool]
+        if negatives == "popularity":
+            counts = item_counts(ds) if counts is None else counts
+            if len(counts) != 2 or any(len(c) != len(p) for c, p in zip(counts, ds.pool)):
+                raise ValueError("counts must be a pair aligned with ds.pool: " + " and ".join(str(len(p)) for p in ds.pool) + " entries")
+            cums = [popularity_weights(c, power)[1] for c in counts]
+            self.cum, self.total = [to(c) for c in cums], [int(c[-1]) for c in cums]
         off = np.zeros(len(ds) + 1, dtype=np.int32)
         np.cumsum([len(o) for o in ds.own_items], out=off[1:])
         self.own_off = torch.from_numpy(off).to(self.device)
@@ -155,7 +204,11 @@ class DeviceBatches:
     def sample_negatives(self) -> torch.Tensor:
         """[N, k] negatives for one epoch, drawn ON THE DEVICE (amid_sample_negatives_i64): uniform without replacement from the
         row's domain pool minus its own sequence -- the reference's random.sample(pool - set(seq), k) (dataset_seq.py:198, :215).
-        Every rank of a data-parallel run draws the same table (same seed, same epoch counter)."""
+        Every rank of a data-parallel run draws the same table (same seed, same epoch counter).
+        negatives="popularity": amid_sample_negatives_weighted_i64 instead -- successive sampling without replacement, each pick
+        proportional to its weight among what is left.  A skewed distribution can leave a row short after the kernel's 4096 rounds
+        although enough ids are eligible, so this mode reads column 0 once per draw (one host synchronisation per epoch) and raises
+        RuntimeError naming the first short row; the uniform mode never looks."""
         if self.negatives == "fixture":
             self.epoch += 1
             return torch.from_numpy(np.ascontiguousarray(self.ds.ref_neg[:, : self.k])).to(self.device)
@@ -163,6 +216,17 @@ class DeviceBatches:
         N = len(self.ds)
         out = torch.empty(N, self.k, dtype=torch.int64, device=self.device)
         self.epoch += 1
+        if self.negatives == "popularity":
+            lib().call("amid_sample_negatives_weighted_i64", self.pool[0].data_ptr(), self.cum[0].data_ptr(), self.pool[0].numel(),
+                       self.pool[1].data_ptr(), self.cum[1].data_ptr(), self.pool[1].numel(), self.total[0], self.total[1],
+                       self.own.data_ptr(), self.own_off.data_ptr(), self.t["domain_id"].data_ptr(), N, self.k, self.seed, self.epoch,
+                       out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+            short = torch.nonzero(out[:, 0] < 0).reshape(-1)
+            if short.numel():
+                raise RuntimeError(f"popularity-weighted negatives: row {int(short[0])} (and {short.numel() - 1} more) found fewer than "
+                                   f"{self.k} ids in 4096 rounds of epoch {self.epoch}: the weights are too skewed for this k "
+                                   "(lower the power, or k)")
+            return out
         lib().call("amid_sample_negatives_i64", self.pool[0].data_ptr(), self.pool[0].numel(), self.pool[1].data_ptr(),
                    self.pool[1].numel(), self.own.data_ptr(), self.own_off.data_ptr(), self.t["domain_id"].data_ptr(), N, self.k,
                    self.seed, self.epoch, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)

@@ -332,6 +332,7 @@ def main(argv=None):
     if (args.exclude_history or args.list_scores) and not args.candidates:
         raise SystemExit("--exclude_history and --list_scores belong to --candidates")
     check_diversify(args)
+    base.check_neg_sampling(args)
     cls ={"gru4rec": GRU4Rec, "sasrec": SASRec, "bert4rec": BERT4Rec}.get(args.model.lower())
     if cls is None:
         raise SystemExit(f"unknown --model {args.model!r} (gru4rec | sasrec | bert4rec)")
@@ -353,11 +354,13 @@ def main(argv=None):
     print(f"{args.weights}: {kind}; {len(ds)} rows of {users_csv}")
     dev = torch.device(args.device)
     pool = None
-    if args.pool == "dataset":
+    neg_eval = args.metrics and args.neg_sampling == "popularity" and args.neg_sampling_for in ("both", "eval")
+    if args.pool == "dataset" or neg_eval:
         train_csv = os.path.join(root, f"{args.domain_type}_train{int(args.overlap_ratio * 100)}.csv")
         ds_train = DualDomainSeqDataset(seq_len=args.seq_len, isTrain=True, neg_nums=1, long_length=args.long_length, pad_id=item_length + 1,
                                         seed=0, csv_path=train_csv)
-        pool = tuple(torch.from_numpy(p).to(dev) for p in ds_train.pool)                  # sorted unique (dataset_seq.py:141-142)
+        if args.pool == "dataset":
+            pool = tuple(torch.from_numpy(p).to(dev) for p in ds_train.pool)              # sorted unique (dataset_seq.py:141-142)
     s1, s2 = ds.seq_d1, ds.seq_d2
     if args.history == "full":
         s1, s2 = full_history(s1, s2, ds.i_node, ds.domain_id)
@@ -408,7 +411,8 @@ def main(argv=None):
         out["vectors"] = vectors
     out["metrics"] = None
     if args.metrics:
-        val = DeviceBatches(ds, args.bs, shuffle=False, device=args.device, seed=0)
+        val = DeviceBatches(ds, args.bs, shuffle=False, device=args.device, seed=0,
+                            **(base.neg_loader_args(args, "eval", ds, ds_train) if neg_eval else {}))
         res = base.test(model, args, val)
         names = ("HR@1", "NDCG@1", "HR@5", "NDCG@5", "HR@10", "NDCG@10", "MRR")
         for key, sc in res.items():

@@ -6,7 +6,9 @@ ignored; ``type=bool`` flags keep the reference's "any non-empty string is True"
 constants (item_length 447 410, pad id item_length + 1, table of 2 x item_length rows, drop_last on both
 loaders, five seeds 0..4, loss logged every 20 iterations, best-so-far HR/NDCG/MRR per epoch).
 Additions: ``--data_root`` (the reference hard-codes /ossfs/workspace/CDSR), ``--seeds``, ``--device``,
-``--no_graph``, ``--no_pool``, ``--max_steps``, ``--dtype {fp32,bf16}``; data parallel when launched by ``python -m torch.distributed.run --nproc-per-node N``
+``--no_graph``, ``--no_pool``, ``--max_steps``, ``--dtype {fp32,bf16}``, ``--neg_sampling {uniform,popularity}`` with ``--neg_power P``
+(0 .. 1, default 1.0) and ``--neg_sampling_for {both,train,eval}`` (negatives drawn in proportion to count ** P in the training CSV
+instead of uniformly: DESIGN.md section 16); data parallel when launched by ``python -m torch.distributed.run --nproc-per-node N``
 (one process per GPU, RCCL, ``--bs`` per GPU; BASELINE.json configs[3]).
 
     python train_sr.py --data_root /path/to/AMID -ds amazon -dm cloth_sport --overlap_ratio 0.75 \
@@ -23,7 +25,7 @@ import time
 import numpy as np
 import torch
 
-from .dataset_seq import DeviceBatches, DualDomainSeqDataset, JointBatches
+from .dataset_seq import DeviceBatches, DualDomainSeqDataset, JointBatches, item_counts
 from .model_gru import GRU4Rec, GRU4RecAMID
 from .model_seq import BERT4Rec, SASRec
 from .utils import AverageMeter, device_positive_ranks, init_logger, scores_from_ranks
@@ -33,6 +35,14 @@ FIX_VALUE = 1e-7          # train_sr.py:42: ties between the positive and a nega
 
 
 STEPS_PER_GRAPH = 4          # train(): consecutive pooled steps per replayed hipGraph (single GPU)
+
+
+class _NegFlag(argparse.Action):
+    """Stores the value and notes that the flag was given (check_neg_sampling: --neg_power / --neg_sampling_for need popularity)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        namespace.neg_flags_given = namespace.neg_flags_given + (option_string,)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -79,6 +89,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="fp32: exact fp32 matrix products; bf16: bf16 MFMA operands, fp32 accumulation and storage (sasrec, emb_dim 128)")
     p.add_argument("--full_rank", action="store_true", help="also rank every positive against its domain's whole item pool (minus the "
                                                             "user's own items) and log those metrics as d1_full / d2_full")
+    p.add_argument("--neg_sampling", type=str, default="uniform", choices=("uniform", "popularity"),
+                   help="uniform: negatives uniform over pool minus own (the reference); popularity: in proportion to count ** --neg_power, "
+                        "counted in the training CSV, without replacement")
+    p.add_argument("--neg_power", type=float, default=1.0, action=_NegFlag, help="--neg_sampling popularity: 0 .. 1 (0 is uniform)")
+    p.add_argument("--neg_sampling_for", type=str, default="both", choices=("both", "train", "eval"), action=_NegFlag,
+                   help="--neg_sampling popularity: which loaders draw that way (the others stay uniform)")
+    p.set_defaults(neg_flags_given=())
     p.add_argument("--save_dir", type=str, default=None,
                    help="write DIR/seed{i}/best_d1.pt and best_d2.pt (weights only, kept when MRR_d1 / MRR_d2 >= the best so far; held as "
                         "device copies until the seed's run ends: two extra table-sized buffers in HBM) and DIR/seed{i}/last.pt (the "
@@ -89,8 +106,28 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 # what a last.pt must share with the command line that resumes it
-RESUME_KEYS = ("model", "emb_dim", "seq_len", "hid_dim", "isItC", "isInC", "dtype", "dataset_type", "domain_type", "bs", "overlap_ratio")
+RESUME_KEYS = ("model", "emb_dim", "seq_len", "hid_dim", "isItC", "isInC", "dtype", "dataset_type", "domain_type", "bs", "overlap_ratio",
+               "neg_sampling", "neg_power", "neg_sampling_for")
 _FLAGS = {"dataset_type": "-ds", "domain_type": "-dm"}
+# what a last.pt written before a key existed counts as
+_RESUME_DEFAULTS = {"neg_sampling": "uniform", "neg_power": 1.0, "neg_sampling_for": "both"}
+
+
+def check_neg_sampling(args) -> None:
+    """--neg_sampling / --neg_power / --neg_sampling_for against each other: SystemExit before any GPU work."""
+    if args.neg_sampling != "popularity" and args.neg_flags_given:
+        raise SystemExit(f"{args.neg_flags_given[0]} belongs to --neg_sampling popularity")
+    if not 0.0 <= args.neg_power <= 1.0:
+        raise SystemExit(f"--neg_power must be in 0..1, got {args.neg_power}")
+
+
+def neg_loader_args(args, role: str, ds=None, ds_train=None) -> dict:
+    """DeviceBatches' negatives / counts / power for a loader of `role` ("train" | "eval").  A training loader weighs by its own
+    dataset's counts; an evaluation loader over `ds` by the training dataset's (`ds_train`), mapped onto its pools by id."""
+    if args.neg_sampling != "popularity" or args.neg_sampling_for not in ("both", role):
+        return {}
+    counts = item_counts(ds_train, onto=ds.pool) if role == "eval" else None
+    return {"negatives": "popularity", "counts": counts, "power": args.neg_power}
 
 
 def run_signature(args, keys=RESUME_KEYS) -> dict:
@@ -107,8 +144,9 @@ def read_resume(args, keys=RESUME_KEYS):
     ck = torch.load(args.resume, map_location="cpu", weights_only=True)
     saved = ck.get("extra", {}).get("args", {})
     for k, v in run_signature(args, keys).items():
-        if saved.get(k) != v:
-            raise SystemExit(f"--resume {args.resume}: {_FLAGS.get(k, '--' + k)} is {v!r} here but {saved.get(k)!r} in the file")
+        was = saved.get(k, _RESUME_DEFAULTS.get(k))
+        if was != v:
+            raise SystemExit(f"--resume {args.resume}: {_FLAGS.get(k, '--' + k)} is {v!r} here but {was!r} in the file")
     return ck
 
 
@@ -360,6 +398,7 @@ def init_data_parallel(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    check_neg_sampling(args)
     ck = read_resume(args)
     rank, world = init_data_parallel(args)
     summary = list(ck["extra"]["summary"]) if ck is not None else []
@@ -386,10 +425,12 @@ def main(argv=None):
             if j:
                 ds_train.shift_items(item_length + 2)
                 ds_val.shift_items(item_length + 2)
-            trains.append(DeviceBatches(ds_train, args.bs, shuffle=True, device=args.device, seed=i, rank=rank, world=world))
+            trains.append(DeviceBatches(ds_train, args.bs, shuffle=True, device=args.device, seed=i, rank=rank, world=world,
+                                        **neg_loader_args(args, "train")))
             # (isItC under data parallel: InterComp's Linear(bs, 1) is built for the GLOBAL batch of world x --bs rows, so the
             # evaluation, which every rank runs whole, steps through batches of that size)
-            vals.append(DeviceBatches(ds_val, args.bs * (world if (args.isItC or args.isInC) else 1), shuffle=False, device=args.device, seed=i))
+            vals.append(DeviceBatches(ds_val, args.bs * (world if (args.isItC or args.isInC) else 1), shuffle=False, device=args.device, seed=i,
+                                      **neg_loader_args(args, "eval", ds_val, ds_train)))
         if len(parts) == 2:
             # joint mode: the second dataset's ids sit item_length + 2 rows behind the first's in the reference-sized table of
             # 2 * item_length rows (train_sr.py:456) -- checked here, on the host, before any step runs (the fused step would only flag an

@@ -136,6 +136,7 @@ def main(argv=None):
     # one process per GPU under `python -m torch.distributed.run --nproc-per-node N train_sr_dr.py ...` (the reference is single-GPU):
     # --bs is the batch PER GPU, both loops shard their batches by rank and exchange gradients every step (amid_amd/dist.py); with
     # --isItC (run.sh) InterComp's Linear(bs, 1) spans the GLOBAL batch of world x --bs rows (engine._enqueue_user_vectors)
+    base.check_neg_sampling(args)
     ck = base.read_resume(args, RESUME_KEYS)
     rank, world = base.init_data_parallel(args)
     if world > 1 and args.model.lower() != "sasrec":
@@ -152,9 +153,10 @@ def main(argv=None):
                                                                long_length=args.long_length, pad_id=item_length + 1, seed=seed, csv_path=path)
         ds_train, ds_dr = mk(stem + ".csv", True, i), mk(stem + "_DR.csv", True, 500 + i)            # :635-640
         ds_val = mk(os.path.join(root, f"{args.domain_type}_test.csv"), False, 1000 + i)
-        train_batches = DeviceBatches(ds_train, args.bs, shuffle=True, device=args.device, seed=i, rank=rank, world=world)
-        train_batches_dr = DeviceBatches(ds_dr, args.bs, shuffle=True, device=args.device, seed=500 + i, rank=rank, world=world)
-        val_batches = DeviceBatches(ds_val, gbs, shuffle=False, device=args.device, seed=i)
+        neg_train = base.neg_loader_args(args, "train")          # (each training loader weighs by its own dataset's counts)
+        train_batches = DeviceBatches(ds_train, args.bs, shuffle=True, device=args.device, seed=i, rank=rank, world=world, **neg_train)
+        train_batches_dr = DeviceBatches(ds_dr, args.bs, shuffle=True, device=args.device, seed=500 + i, rank=rank, world=world, **neg_train)
+        val_batches = DeviceBatches(ds_val, gbs, shuffle=False, device=args.device, seed=i, **base.neg_loader_args(args, "eval", ds_val, ds_train))
         torch.cuda.set_device(torch.device(args.device))
         model = classes[args.model.lower()](user_length=2 * user_length, user_emb_dim=args.emb_dim, item_length=2 * item_length, item_emb_dim=args.emb_dim,
                        seq_len=args.seq_len, hid_dim=args.hid_dim, bs=gbs, isInC=args.isInC, isItC=args.isItC, threshold1=args.ts1,

@@ -399,6 +399,19 @@ int amid_transpose_rect_f32(const float* const* src, float* const* dst, const in
 int amid_sample_negatives_i64(const long long* pool_d1, int n_pool_d1, const long long* pool_d2, int n_pool_d2,
                               const long long* own_items, const int* own_off, const long long* domain_id, int N, int k,
                               unsigned long long seed, unsigned epoch, long long* out, void* stream);
+/* The same draw with every pool entry weighted (popularity-weighted negatives; not in the reference).  cum_d*: inclusive prefix sums
+ * of the entries' positive integer weights, aligned with pool_d*; total_d* = cum_d*[n_pool_d* - 1], 0 < total < 2^62 (else
+ * AMID_ERR_ARG).  Row r, round, lane make one Philox call (r << 20) | (round << 6) | lane at site 0x4E57 with step word = epoch;
+ * r64 = (x << 32) | y of its first two words, t = (r64 * total) >> 64 (the high half of the 64 x 64 product) and the candidate is
+ * pool[j] for the first j with cum[j] > t.  Acceptance, the k <= 2048 limit and the out[r][0] = -1 mark are those of
+ * amid_sample_negatives_i64; rejecting repeats makes it successive sampling without replacement (each pick proportional to its
+ * weight among what is left).  A skewed prefix can leave a row short after the 4096 rounds although enough ids are eligible: the
+ * caller reads out[r][0] (DeviceBatches does).  Host restatement: tests/sampler_weighted_ref.py. */
+int amid_sample_negatives_weighted_i64(const long long* pool_d1, const long long* cum_d1, int n_pool_d1,
+                                       const long long* pool_d2, const long long* cum_d2, int n_pool_d2,
+                                       long long total_d1, long long total_d2,
+                                       const long long* own_items, const int* own_off, const long long* domain_id,
+                                       int N, int k, unsigned long long seed, unsigned epoch, long long* out, void* stream);
 
 /* ---- InterComp on the SASRec path (isItC; next-1 of SURVEY.md 8(f)) -------------------------------------------------------
  * replaces: InterComp.forward model_seq.py:483-497 as used at model_seq.py:426-434 (both directions) and its autograd.  Since
