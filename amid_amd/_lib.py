@@ -10,6 +10,7 @@ resolved, importing the compute path raises (``AmidLibraryError``).
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
 import re
 from typing import Dict, List, Tuple
@@ -79,8 +80,8 @@ class Binder:
     """Named arguments -> the positional order of a prototype.  The values come from `tables` (mappings parameter name -> value: the
     engines' named pointer tables; names the entry point does not take are ignored, which is how one table serves entry points that
     take a subset of it) and from `args` (every name must be a parameter).  Every parameter must be supplied exactly once -- null is
-    an explicit None --, otherwise TypeError naming the entry point and the parameter: nothing is launched.  The order is resolved once
-    per (entry point, names supplied by each source); after that a bind is one tuple build."""
+    an explicit None --, otherwise TypeError naming the entry point and the parameter: nothing is launched.  That is checked once per
+    (entry point, names supplied by each source); after that a bind merges the sources and picks the parameters in order."""
 
     def __init__(self, protos) -> None:
         self._params = {entry: tuple(p[2]) for entry, p in protos.items()}
@@ -88,27 +89,43 @@ class Binder:
 
     def bind(self, entry: str, tables, args) -> tuple:
         key = (entry, tuple(map(tuple, tables)), tuple(args))
-        order = self._orders.get(key)
-        if order is None:
-            order = self._orders[key] = self._resolve(entry, tables, args)
-        srcs = (*tables, args)
-        return tuple([srcs[i][n] for i, n in order])
+        pick = self._orders.get(key)
+        if pick is None:
+            pick = self._orders[key] = self._resolve(entry, tables, args)
+        merged = {}
+        for t in tables:
+            merged.update(t)
+        merged.update(args)
+        return pick(merged)
 
-    def _resolve(self, entry: str, tables, args) -> list:
+    def _resolve(self, entry: str, tables, args):
+        """The check of one (entry point, names supplied by each source): every parameter from exactly one source.  Returns what picks the
+        parameters, in the prototype's order, out of the sources merged into one mapping (no name is in two of them: checked here)."""
         params = self._params.get(entry)
         if params is None:
             raise TypeError(f"{entry} is not declared in include/amid_hip.h")
         for n in args:
             if n not in params:
                 raise TypeError(f"{entry} has no parameter {n!r}")
-        order = []
         for n in params:
             at = [i for i, src in enumerate((*tables, args)) if n in src]
             if len(at) != 1:
                 raise TypeError(f"{entry}: parameter {n!r} " + ("is not supplied (null is an explicit None)" if not at else
                                                                f"is supplied {len(at)} times"))
-            order.append((at[0], n))
-        return order
+        if len(params) < 2:          # (itemgetter gives a bare value for one name and takes no empty list)
+            return lambda merged: tuple(merged[n] for n in params)
+        return operator.itemgetter(*params)
+
+
+def prefixed(prefix: str, table) -> dict:
+    """`table` under the names an entry point spells with `prefix`: the fused feed-forward chain of the q / k / v backward (fh, fr, fln_w ...),
+    the next layer's q / k / v of an out-projection / feed-forward forward (nln_w, nqn ...)."""
+    return {prefix + k: v for k, v in table.items()}
+
+
+def absent(table, **scalars) -> dict:
+    """An optional block an entry point is not given: every name of `table` as an explicit null (`scalars`: the block's by-value parameters)."""
+    return {**dict.fromkeys(table), **scalars}
 
 
 def declared_symbols() -> List[str]:

@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from ._lib import lib, ptr_array
+from ._lib import absent, lib, prefixed, ptr_array
 
 from .engine_dp import DataParallelMixin, HipMergeBackend      # noqa: F401  (re-exported)
 from .engine_graph import GraphMixin
@@ -40,8 +40,16 @@ SASREC_FAMILIES = (("ln1_w", "attention_layernorms.{l}.weight"), ("ln1_b", "atte
                    ("ln2_w", "forward_layernorms.{l}.weight"), ("ln2_b", "forward_layernorms.{l}.bias"),
                    ("w1", "forward_layers.{l}.conv1.weight"), ("b1", "forward_layers.{l}.conv1.bias"),
                    ("w2", "forward_layers.{l}.conv2.weight"), ("b2", "forward_layers.{l}.conv2.bias"))
-QKV_FAMILIES = tuple(n for n, _ in SASREC_FAMILIES[:4])
-FFN_FAMILIES = tuple(n for n, _ in SASREC_FAMILIES[4:])
+# optional blocks a launch is not given (explicit nulls under the header's names): the weight-image riders, the sort riders
+NO_W16_RIDERS = absent(("w_src", "w16_dst", "w16t_dst"), n_w=0, w_planes=0)
+NO_SORT_RIDERS = absent(("sort_plan",), sort_phase=0)
+NO_PACK = absent(("out_ids", "dense_src", "dense_dst", "err_flag"), n_out=0, pad_id=0, dense_n=0)      # a gradient tail that packs no exchange chunk
+NO_UNIQ = absent(("uniq_ids", "n_uniq"))
+NO_POS_ROWS = absent(("live", "dpos0", "dpos1"), B=0, T=0)          # a gradient tail whose reduce table holds the position rows' partial sums
+NO_SCORER_SUMS = absent(("hidg", "u", "items", "dW1", "db1", "dW2", "db2"), NI=0, hid=0)
+NO_FUSED_FFN = absent(("tmq", "step_state") + tuple("f" + n for n in ("h", "r", "ln_w", "w1T", "w2T", "woT", "dpre2", "dpre1", "dr", "d_o", "ln_part")),
+                      flayer=0, train=0, p_drop=0.0)          # (the q / k / v backward of layer 0: no feed-forward chain below it)
+NO_NEXT_QKV = absent(prefixed("n", dict.fromkeys(("qn", "q", "k", "v", "ln_w", "ln_b", "w_in", "b_in"))))
 
 
 class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
@@ -297,6 +305,96 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
                                     ln1_part=pa(pl.ln1_part_s), ln2_part=pa(pl.ln2_part_s))
         return pl.seq_grad_ptrs
 
+    @staticmethod
+    def _on_plan(pl: SasrecPlan, name: str, build):
+        """A table of the plan's own tensors, built once (a plan's buffers never move)."""
+        t = pl.__dict__.get(name)
+        if t is None:
+            t = pl.__dict__[name] = build()
+        return t
+
+    def _marshal(self, pl: SasrecPlan):
+        """The index marshal's batch: the plan's static inputs, their packed image and the lists the packing launches write (T: the
+        batch's own sequence length, not the encoders')."""
+        shp, p = pl.shape, lambda n: getattr(pl, n).data_ptr()          # noqa: E731
+        return self._on_plan(pl, "marshal_tab", lambda: dict(
+            i_node=p("in_i_node"), neg=p("in_neg"), seq_d1=p("in_seq_d1"), seq_d2=p("in_seq_d2"), in_pack=p("in_pack"), in_words=pl.in_words,
+            B=shp.B, T=shp.T, n_neg=shp.NI - 1, n_rows=self.n_rows, idx_all=p("idx_all"), idx_c=p("idx_c"), row_c=p("row_c"), live=p("live"),
+            domain=p("domain"), err_flag=p("err")))
+
+    def _seg(self, pl: SasrecPlan):
+        """The segment reduce of the table-row gradients: the rows, the sorted positions and their runs, the workspace, the reduced rows."""
+        return self._on_plan(pl, "seg_tab", lambda: dict(
+            grad_rows=pl.dxg.data_ptr(), pos_sorted=pl.pos_sorted.data_ptr(), seg_off=pl.seg_off.data_ptr(), seg_of=pl.seg_of.data_ptr(),
+            workspace=pl.seg_ws.data_ptr(), uniq_grad=pl.uniq_grad.data_ptr()))
+
+    def _uniq(self, pl: SasrecPlan):
+        """The step's unique rows: their ids and their count."""
+        return self._on_plan(pl, "uniq_tab", lambda: dict(uniq_ids=pl.uniq_ids.data_ptr(), n_uniq=pl.n_uniq.data_ptr()))
+
+    def _saved(self, pl: SasrecPlan, l: int):
+        """What layer `l`'s forward saves for its backward, under the strip and row-tile entries' names (xo: the layer's output)."""
+        return self._on_plan(pl, f"saved_tab{l}", lambda: dict(
+            {n: getattr(pl, n)[l].data_ptr() for n in ("x", "qn", "q", "k", "v", "o", "stats", "r", "y", "h")}, xo=pl.x[l + 1].data_ptr()))
+
+    def _qkv_block(self, pl: SasrecPlan, l: int, pre: str = ""):
+        """Layer `l`'s LayerNorm + q / k / v under its own launch's names; pre = "n": as the next layer's block of the launch in front of it."""
+        lay = self._lay()[l]
+        return self._on_plan(pl, f"qkv_tab{l}{pre}", lambda: prefixed(pre, dict(
+            {n: getattr(pl, n)[l].data_ptr() for n in ("qn", "q", "k", "v")}, ln_w=lay["ln1_w"], ln_b=lay["ln1_b"], w_in=lay["w_in"], b_in=lay["b_in"])))
+
+    def _ffn_bwd_block(self, pl: SasrecPlan, l: int, rows: bool, fused: bool = False):
+        """Layer l's feed-forward / out-projection backward under its own launch's names: what it reads, the transposes in the form this
+        backward multiplies (_wT), what it writes.  rows: the row-tile kernels' partials over the live rows.  fused: under the names of the
+        q / k / v backward of the layer above, which runs this chain in the same launch (fh, fr, fln_w ...)."""
+        kind = f"{int(self._p3_bwd)}{int(self._bf16_bwd)}{int(bool(rows))}"
+        if fused:
+            return self._on_plan(pl, f"fused_ffn_bwd_tab{l}{kind}", lambda: prefixed("f", self._ffn_bwd_block(pl, l, rows)))
+        return self._on_plan(pl, f"ffn_bwd_tab{l}{kind}", lambda: dict(
+            self._grads(pl, l), h=pl.h[l].data_ptr(), r=pl.r[l].data_ptr(), ln_w=self._pp(f"sac{{d}}.forward_layernorms.{l}.weight"),
+            w1T=self._wT(l, 4), w2T=self._wT(l, 5), woT=self._wT(l, 3), layer=l, d_o=pl.d_o.data_ptr(),
+            ln_part=(pl.ln2_part_v if rows else pl.ln2_part)[l].data_ptr()))
+
+    def _qkv_bwd_block(self, pl: SasrecPlan, l: int, rows: bool):
+        """... and its q / k / v + LayerNorm1 backward."""
+        kind = f"{int(self._p3_bwd)}{int(self._bf16_bwd)}{int(bool(rows))}"
+        return self._on_plan(pl, f"qkv_bwd_tab{l}{kind}", lambda: dict(
+            self._grads(pl, l), x=pl.x[l].data_ptr(), ln_w=self._pp(f"sac{{d}}.attention_layernorms.{l}.weight"), wqT=self._wT(l, 0),
+            wkT=self._wT(l, 1), wvT=self._wT(l, 2), ln_part=(pl.ln1_part_v if rows else pl.ln1_part)[l].data_ptr()))
+
+    def _grads(self, pl: SasrecPlan, l: int):
+        """Layer `l`'s gradient outputs (d_o and the encoder-input gradient are shared by the layers: given by name)."""
+        return self._on_plan(pl, f"grads_tab{l}", lambda: dict(
+            dq=pl.dq_l[l].data_ptr(), dk=pl.dk_l[l].data_ptr(), dv=pl.dv_l[l].data_ptr(), dr=pl.dr[l].data_ptr(), dpre1=pl.dpre1[l].data_ptr(),
+            dpre2=pl.dpre2[l].data_ptr()))
+
+    # (the two Adam tables are read from the tensors at every launch, never cached: select_optimizer rebinds them, and a state dropped and
+    # made again by load_training_state has new buffers under its old number)
+    def _adam_dense(self, g: Optional[torch.Tensor] = None):
+        """Dense Adam over the flat buffer with the current state's moments: p, m, v, g, n (g: the engine's own gradient buffer or a caller's)."""
+        fp = self.dense
+        return dict(p=fp.data.data_ptr(), m=fp.m.data_ptr(), v=fp.v.data_ptr(), g=(fp.grad if g is None else g).data_ptr(), n=fp.numel)
+
+    def _adam_rows(self):
+        """Lazy row Adam: the table, the current state's moments (m_tab, v_tab -- m, v are the dense ones) and the rows' step stamps."""
+        return dict(table=self.table.data_ptr(), m_tab=self.table_m.data_ptr(), v_tab=self.table_v.data_ptr(), last=self.table_last.data_ptr())
+
+    def _dpos(self):
+        """The position rows' gradients."""
+        fp = self.dense
+        return self._cached("dpos", lambda: dict(dpos0=fp.ptr("sac1.pos_emb.weight", fp.grad), dpos1=fp.ptr("sac2.pos_emb.weight", fp.grad)))
+
+    def _k1_head(self, pl: SasrecPlan, pos0, pos1, tmq, tr: int, p_drop: float, n_item_rows: int):
+        """What every form of the gather K1 takes behind the table (the replay form takes the table with its Adam state: _adam_rows)."""
+        shp = pl.shape
+        return dict(idx_all=pl.idx_all.data_ptr(), pos0=pos0, pos1=pos1, B=shp.B, T=shp.Tenc, D=self.D, n_item_rows=n_item_rows,
+                    xg=pl.xg.data_ptr(), tmq=tmq, step_state=self.step_state.data_ptr(), train=tr, p_drop=p_drop, stream=self.s)
+
+    def _w16_riders(self, transposes: bool = True):
+        """The weight images a launch's extra workgroups write: three bf16 planes of the 24 encoder weights (+ of their transposes)."""
+        src, w16 = self._w16_images(3)
+        return dict(w_src=src, n_w=24, w_planes=3, w16_dst=w16.data_ptr(), w16t_dst=self._wT16x3_buf().data_ptr() if transposes else None)
+
     _bf16_bwd = False          # set per backward: the strip backward's products take bf16 images (compute = "bf16" on the strip path)
     _p3_bwd = False            # set per backward: ... three-plane images (compute = "fp32", products on bf16 pieces)
     # compute = "fp32": the strip backward's data-gradient products on the bf16 matrix cores at fp32 accuracy (three bf16 pieces per operand,
@@ -351,12 +449,9 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         pl.gather_on_fwd = False
         pl.prepared = False
         if pl.tail2:
-            pool, phase = ent
             self._ensure_opt_state()
-            head = (pool.data_ptr(), pool.stride(0), pool.shape[0], phase, pl.in_pack.data_ptr(), pl.in_words, shp.B, shp.T,
-                    shp.NI - 1, self.n_rows, pl.idx_all.data_ptr(), pl.idx_c.data_ptr(), pl.row_c.data_ptr(), pl.live.data_ptr(), pl.err.data_ptr(),
-                    self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(), self.D,
-                    self.step_state.data_ptr(), self._sort_plan_c(pl))
+            head = (self._marshal(pl), self._pool_batch(ent), self._adam_rows(),
+                    dict(D=self.D, step_state=self.step_state.data_ptr(), sort_plan=self._sort_plan_c(pl), stream=s))
             # the step's gather as the prologue of its forward (amid_sas_seq_fwd_gather_*_f32): K1's riders -- the weight images of the forward
             # and of the backward strips -- move to this launch's last workgroups
             pl.gather_on_fwd = bool(self.GATHER_ON_FWD and self._fwd_on_pieces(pl, shp.B, shp.Tenc) and self._p3_bwd_for(pl) and shp.T == shp.Tenc)
@@ -365,51 +460,40 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             slabs = self.pool_slabs(pl)
             pl.prepared = bool(self.PREPARED_POOL and slabs is not None and getattr(self, "_in_train_step", False) and self.compute != "bf16")
             if pl.prepared:
-                w = (None, 0, 0, None, None)
-                if pl.gather_on_fwd:
-                    src, w16 = self._w16_images(3)
-                    w = (src, 24, 3, w16.data_ptr(), self._wT16x3_buf().data_ptr())
-                L.call("amid_step_head_prepared_f32", *head, slabs[0].data_ptr(), slabs[0].stride(0), *w, s)
+                L.call_named("amid_step_head_prepared_f32", *head, self._w16_riders() if pl.gather_on_fwd else NO_W16_RIDERS,
+                             slab=slabs[0].data_ptr(), slab_stride=slabs[0].stride(0))
             elif pl.gather_on_fwd:
-                src, w16 = self._w16_images(3)
-                L.call("amid_step_head_w16_f32", *head, src, 24, 3, w16.data_ptr(), self._wT16x3_buf().data_ptr(), s)
+                L.call_named("amid_step_head_w16_f32", *head, self._w16_riders())
             else:
-                L.call("amid_step_head_f32", *head, s)
+                L.call_named("amid_step_head_f32", *head)
             self.step += 1
             pl.compact, pl.riding, pl.chain = True, not pl.prepared, False
             self._sort_owed = False
             return
+        st = self.step_state.data_ptr()
         if ent is not None:
-            pool, phase = ent
             if not bump_step:
                 raise ValueError("an input pool advances with the step counter: enqueue_prepare(bump_step=True) only")
-            if with_live:
-                L.call("amid_pack_indices_pool_live", pool.data_ptr(), pool.stride(0), pool.shape[0], phase, pl.in_pack.data_ptr(),
-                       pl.in_words, shp.B, shp.T, shp.NI - 1, self.n_rows, pl.idx_all.data_ptr(), pl.err.data_ptr(),
-                       self.step_state.data_ptr(), pl.live.data_ptr(), s)
-            else:
-                L.call("amid_pack_indices_pool", pool.data_ptr(), pool.stride(0), pool.shape[0], phase, pl.in_pack.data_ptr(),
-                       pl.in_words, shp.B, shp.T, shp.NI - 1, self.n_rows, pl.idx_all.data_ptr(), pl.err.data_ptr(),
-                       self.step_state.data_ptr(), s)
+            # (the marshal's table holds the live list: the form without one is not given it by a name it does not have)
+            L.call_named("amid_pack_indices_pool_live" if with_live else "amid_pack_indices_pool", self._marshal(pl), self._pool_batch(ent),
+                         step_state=st, stream=s)
             self.step += 1
-            if sparse and (pl.riding or pl.chain):
-                self._sort_owed = False
-            elif sparse:
-                self.ev_idx.record(self.stream)
-                self._sort_owed = bool(defer_sort)
-                if not defer_sort:
-                    self.enqueue_sort(pl)
+            self._sort_behind_pack(pl, sparse, defer_sort)
             return
-        if with_live:
-            L.call("amid_pack_indices_live", pl.in_i_node.data_ptr(), pl.in_neg.data_ptr(), pl.in_seq_d1.data_ptr(), pl.in_seq_d2.data_ptr(),
-                   shp.B, shp.T, shp.NI - 1, self.n_rows, pl.idx_all.data_ptr(), pl.err.data_ptr(),
-                   self.step_state.data_ptr() if bump_step else None, pl.domain.data_ptr(), pl.live.data_ptr(), s)
-        else:
-            L.call("amid_pack_indices", pl.in_i_node.data_ptr(), pl.in_neg.data_ptr(), pl.in_seq_d1.data_ptr(), pl.in_seq_d2.data_ptr(),
-                   shp.B, shp.T, shp.NI - 1, self.n_rows, pl.idx_all.data_ptr(), pl.err.data_ptr(),
-                   self.step_state.data_ptr() if bump_step else None, s)
+        L.call_named("amid_pack_indices_live" if with_live else "amid_pack_indices", self._marshal(pl), step_state=st if bump_step else None, stream=s)
         if bump_step:
             self.step += 1
+        self._sort_behind_pack(pl, sparse, defer_sort)
+
+    @staticmethod
+    def _pool_batch(ent):
+        """The batch an input pool's step reads: (pool, phase) under the header's names."""
+        pool, phase = ent
+        return dict(pool=pool.data_ptr(), pool_stride=pool.stride(0), n_pool=pool.shape[0], phase=phase)
+
+    def _sort_behind_pack(self, pl: SasrecPlan, sparse: bool, defer_sort: bool) -> None:
+        """The step's index sort once the packing launch is enqueued: riding in later launches, or forked onto the side stream here
+        (defer_sort: by the caller, behind the main stream's next kernel)."""
         if sparse and (pl.riding or pl.chain):
             self._sort_owed = False
         elif sparse:
@@ -694,7 +778,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         """The gather K1 of a forward in the variant the step needs: over every sequence or the live list `lf`, writing the compact index
         list, with the folded catch-up (+ phase 1 of a riding sort).  items=False: the sequences' rows only (the evaluation head gathers
         the candidates' rows itself)."""
-        L, s, shp, D = lib(), self.s, pl.shape, self.D
+        L, shp = lib(), pl.shape
         B, T, NI = shp.B, shp.Tenc, shp.NI if items else 0
         st = self.step_state.data_ptr()
         # what this launch's riders write is decided HERE: a flag left by an earlier forward (e.g. a train-mode forward without a backward)
@@ -702,28 +786,24 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         pl.w16_written = pl.wT16x3_written = False
         compact = lf is not None and getattr(pl, "compact", False) and not getattr(pl, "tail2", False)      # (tail2: the step head wrote the list)
         ic, rc = (pl.idx_c.data_ptr(), pl.row_c.data_ptr()) if compact else (None, None)
+        k1, table = self._k1_head(pl, pos0, pos1, tmq, tr, p_drop, B * NI), self.table.data_ptr()
         if getattr(pl, "fold_catchup", False):
             pl.fold_catchup = False
             ride = getattr(pl, "riding", False)
-            L.call("amid_embed_fwd_replay_f32", self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(),
-                   pl.idx_all.data_ptr(), pos0, pos1, B, T, D, B * NI, pl.xg.data_ptr(), tmq, st, tr, p_drop, lf, ic, rc, st,
-                   self._sort_plan(pl) if ride else None, 1 if ride else 0, s)
+            # (the step state twice: the dropout counters' as every K1 form takes it, and the replay's Adam coefficients under a name of its own)
+            L.call_named("amid_embed_fwd_replay_f32", self._adam_rows(), k1, live=lf, idx_c=ic, row_c=rc, adam_state=st,
+                         sort_plan=self._sort_plan(pl) if ride else None, sort_phase=1 if ride else 0)
         elif self._fwd_on_pieces(pl, B, T):          # the gather's extra workgroups write this step's weight images (three bf16 planes each)
-            src, w16 = self._w16_images(3)
-            wt = self._wT16x3_buf() if tr and self._p3_bwd_for(pl) else None     # (+ the transposes' images for this step's backward strips)
-            L.call("amid_embed_fwd_w16_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos0, pos1, B, T, D, B * NI, pl.xg.data_ptr(), tmq, st,
-                   tr, p_drop, lf, ic, rc, src, 24, 3, w16.data_ptr(), wt.data_ptr() if wt is not None else None, s)
+            wt = bool(tr and self._p3_bwd_for(pl))       # (+ the transposes' images for this step's backward strips)
+            L.call_named("amid_embed_fwd_w16_f32", k1, self._w16_riders(transposes=wt), table=table, live=lf, idx_c=ic, row_c=rc)
             pl.w16_written = True
-            pl.wT16x3_written = wt is not None
+            pl.wT16x3_written = wt
         elif compact:
-            L.call("amid_embed_fwd_live_compact_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos0, pos1, B, T, D, B * NI, pl.xg.data_ptr(),
-                   tmq, st, tr, p_drop, lf, ic, rc, s)
+            L.call_named("amid_embed_fwd_live_compact_f32", k1, table=table, live=lf, idx_c=ic, row_c=rc)
         elif lf is not None:
-            L.call("amid_embed_fwd_live_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos0, pos1, B, T, D, B * NI, pl.xg.data_ptr(), tmq, st,
-                   tr, p_drop, lf, s)
+            L.call_named("amid_embed_fwd_live_f32", k1, table=table, live=lf)
         else:
-            L.call("amid_embed_fwd_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos0, pos1, B, T, D, B * NI, pl.xg.data_ptr(), tmq, st, tr,
-                   p_drop, s)
+            L.call_named("amid_embed_fwd_f32", k1, table=table)
         if getattr(self, "_sort_owed", False):      # a deferred side-stream sort starts behind K1 (the compact list is K1's by-product; with
             if compact:                              # the folded catch-up the fork waited so that the main branch is captured first)
                 self.ev_idx.record(self.stream)
@@ -740,18 +820,14 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         pl.fold_catchup = self._fold_catchup(pl) and not chain       # (the chain rides in the catch-up's own launch)
         if pl.fold_catchup:
             return
+        at = dict(idx=pl.idx_all.data_ptr(), n_idx=pl.shape.n_idx, D=self.D, step_state=self.step_state.data_ptr(), stream=self.s)
         if chain:                                 # the step's whole sort rides here (five phases, the riders' own barrier between them)
-            lib().call("amid_lazy_adam_catchup_positions_sort_f32", self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(),
-                       self.table_last.data_ptr(), pl.idx_all.data_ptr(), pl.shape.n_idx, self.D, self.step_state.data_ptr(),
-                       self._sort_plan(pl), 6, self.s)
+            lib().call_named("amid_lazy_adam_catchup_positions_sort_f32", self._adam_rows(), at, sort_plan=self._sort_plan(pl), sort_phase=6)
             return
         if getattr(pl, "riding", False):          # phase 1 of the step's sort rides here
-            lib().call("amid_lazy_adam_catchup_positions_sort_f32", self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(),
-                       self.table_last.data_ptr(), pl.idx_all.data_ptr(), pl.shape.n_idx, self.D, self.step_state.data_ptr(),
-                       self._sort_plan(pl), 1, self.s)
+            lib().call_named("amid_lazy_adam_catchup_positions_sort_f32", self._adam_rows(), at, sort_plan=self._sort_plan(pl), sort_phase=1)
             return
-        lib().call("amid_lazy_adam_catchup_positions_f32", self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(),
-                   self.table_last.data_ptr(), pl.idx_all.data_ptr(), pl.shape.n_idx, self.D, self.step_state.data_ptr(), self.s)
+        lib().call_named("amid_lazy_adam_catchup_positions_f32", self._adam_rows(), at)
 
     def enqueue_forward(self, pl: SasrecPlan, train: bool, with_loss: bool, sum_loss: bool = True, head: bool = True, gather_items: bool = True) -> None:
         """head=False: stop behind the encoders (pl.x[2] is the last layer's output); gather_items=False: the candidates' rows are not gathered
@@ -802,16 +878,18 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             else:
                 self._enqueue_k1(pl, fp.ptr("sac1.pos_emb.weight"), fp.ptr("sac2.pos_emb.weight"), pl.tmq.data_ptr(), tr, SASREC_P_DROP, lf, gather_items)
         lay = self._lay()
-        qkv0, qkv1 = (tuple(lay[l][n] for n in QKV_FAMILIES) for l in (0, 1))
-        rest0, rest1 = (tuple(lay[l][n] for n in FFN_FAMILIES) for l in (0, 1))
+        att = dict(B=B, T=T, D=D, H=self.H, causal=1, step_state=st, train=tr, p_drop=SASREC_P_DROP, stream=s)
 
         def attn_fwd(l):
             if live_fwd:
-                L.call("amid_attn_fwd_live_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), B, T, D, self.H, 1, l, st, tr,
-                       SASREC_P_DROP, pl.o[l].data_ptr(), pl.stats[l].data_ptr(), lf, s)
+                L.call_named("amid_attn_fwd_live_f32", self._saved(pl, l), att, layer=l, live=lf)
             else:
-                L.call("amid_attn_fwd_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), None, B, T, D, self.H, 1, l, st, tr,
-                       SASREC_P_DROP, pl.o[l].data_ptr(), pl.stats[l].data_ptr(), s)
+                L.call_named("amid_attn_fwd_f32", self._saved(pl, l), att, layer=l, key_keep=None)
+
+        # a layer's out-projection + feed-forward launch of the strip and row-tile forms: it computes the NEXT layer's LayerNorm + q / k / v
+        # too (behind the last layer: an absent block)
+        ffn = lambda l: (lay[l], self._saved(pl, l), self._qkv_block(pl, 1, "n") if l == 0 else NO_NEXT_QKV,      # noqa: E731
+                         dict(ln_w=lay[l]["ln2_w"], ln_b=lay[l]["ln2_b"], layer=l, tmq=pl.tmq.data_ptr(), step_state=st, train=tr, p_drop=SASREC_P_DROP))
 
         if pl.strip and self.SEQ_FORWARD and not self.inc_bs and L.value("amid_sas_seq_supported", B, T, D, self.H):
             # the whole encoder -- both layers, attention cores included -- as ONE launch, a workgroup per sequence (csrc/sasrec_seq.hip)
@@ -862,30 +940,21 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             else:
                 L.call_named("amid_sas_seq_fwd_f32", sv, fams, enc, xout=pl.x[2].data_ptr())
         elif pl.strip:       # register-resident strip chains (csrc/sasrec_strip.hip): same operations, operands and saved tensors
-            L.call("amid_sas_strip_qkv_fwd_f32", pl.x[0].data_ptr(), *qkv0, SASREC_LN_EPS, B, T, D, lf, pl.qn[0].data_ptr(), pl.q[0].data_ptr(),
-                   pl.k[0].data_ptr(), pl.v[0].data_ptr(), s)
+            dims = dict(ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, live=lf, stream=s)
+            L.call_named("amid_sas_strip_qkv_fwd_f32", self._qkv_block(pl, 0), dims, x=pl.x[0].data_ptr())
             attn_fwd(0)
-            L.call("amid_sas_strip_oproj_ffn_fwd_f32", pl.o[0].data_ptr(), pl.qn[0].data_ptr(), *rest0, pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, lf,
-                   0, st, tr, SASREC_P_DROP, pl.r[0].data_ptr(), pl.y[0].data_ptr(), pl.h[0].data_ptr(), pl.x[1].data_ptr(), *qkv1,
-                   pl.qn[1].data_ptr(), pl.q[1].data_ptr(), pl.k[1].data_ptr(), pl.v[1].data_ptr(), s)
+            L.call_named("amid_sas_strip_oproj_ffn_fwd_f32", *ffn(0), dims)
             attn_fwd(1)
-            L.call("amid_sas_strip_oproj_ffn_fwd_f32", pl.o[1].data_ptr(), pl.qn[1].data_ptr(), *rest1, pl.tmq.data_ptr(), SASREC_LN_EPS, B, T, D, lf,
-                   1, st, tr, SASREC_P_DROP, pl.r[1].data_ptr(), pl.y[1].data_ptr(), pl.h[1].data_ptr(), pl.x[2].data_ptr(), None, None, None,
-                   None, None, None, None, None, s)
+            L.call_named("amid_sas_strip_oproj_ffn_fwd_f32", *ffn(1), dims)
         else:
-            L.call("amid_sas_qkv_fwd_f32" + pl.rt_suffix, pl.x[0].data_ptr(), *qkv0, SASREC_LN_EPS, M, D, pl.rpt, pl.qn[0].data_ptr(), pl.q[0].data_ptr(),
-                   pl.k[0].data_ptr(), pl.v[0].data_ptr(), self.mma_bf16, s)
+            dims = dict(ln_eps=SASREC_LN_EPS, M=M, D=D, rows_per_tile=pl.rpt, mma_bf16=self.mma_bf16, stream=s)
+            L.call_named("amid_sas_qkv_fwd_f32" + pl.rt_suffix, self._qkv_block(pl, 0), dims, x=pl.x[0].data_ptr())
             for l in (0, 1):
                 attn_fwd(l)
-                rest = rest0 if l == 0 else rest1
                 if l == 0:      # layer 0's out-projection + feed-forward and layer 1's LayerNorm + q / k / v: one launch
-                    L.call("amid_sas_oproj_ffn_qkv_fwd_f32" + pl.rt_suffix, pl.o[0].data_ptr(), pl.qn[0].data_ptr(), *rest, pl.tmq.data_ptr(), SASREC_LN_EPS, M, D,
-                           pl.rpt, 0, st, tr, SASREC_P_DROP, pl.r[0].data_ptr(), pl.y[0].data_ptr(), pl.h[0].data_ptr(), pl.x[1].data_ptr(),
-                           *qkv1, pl.qn[1].data_ptr(), pl.q[1].data_ptr(), pl.k[1].data_ptr(), pl.v[1].data_ptr(), self.mma_bf16, s)
+                    L.call_named("amid_sas_oproj_ffn_qkv_fwd_f32" + pl.rt_suffix, *ffn(0), dims)
                 else:
-                    L.call("amid_sas_oproj_ffn_fwd_f32" + pl.rt_suffix, pl.o[l].data_ptr(), pl.qn[l].data_ptr(), *rest, pl.tmq.data_ptr(), SASREC_LN_EPS, M, D,
-                           pl.rpt, l, st, tr, SASREC_P_DROP, pl.r[l].data_ptr(), pl.y[l].data_ptr(), pl.h[l].data_ptr(), pl.x[l + 1].data_ptr(),
-                           self.mma_bf16, s)
+                    L.call_named("amid_sas_oproj_ffn_fwd_f32" + pl.rt_suffix, *ffn(l), dims)
         if not head:
             return
         if not gather_items:
@@ -1043,13 +1112,14 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         if self.dr:
             outs += [(pl.ips1, pl.ips2, pl.dips1, pl.dips2, pl.sc_part_ips), (pl.g1, pl.g2, pl.dg1, pl.dg2, pl.sc_part_g)]
         pa = lambda seq: ptr_array(list(seq))          # noqa: E731
-        lib().call("amid_scorer_multi_fwd_bwd_f32", pl.u.data_ptr(), items, pa(fp.ptr(f"{h}.fc.0.weight") for h in heads),
-                   pa(fp.ptr(f"{h}.fc.0.bias") for h in heads), pa(fp.ptr(f"{h}.fc.2.weight") for h in heads),
-                   pa(fp.ptr(f"{h}.fc.2.bias") for h in heads), len(heads), pl.labels.data_ptr(), pl.domain.data_ptr(),
-                   pl.in_ob.data_ptr() if self.dr else None, self.dr_mode if self.dr else 0, self.dr_e_w, shp.B, shp.NI, self.D, self.hid,
-                   pa(o[0].data_ptr() for o in outs), pa(o[1].data_ptr() for o in outs), pa(o[2].data_ptr() for o in outs),
-                   pa(o[3].data_ptr() for o in outs), pl.loss_part.data_ptr(), pl.dr_loss_part.data_ptr() if self.dr else None,
-                   pl.du.data_ptr(), ditems, pa(o[4].data_ptr() for o in outs), tr_src, tr_dst, n_tr, self.s)
+        lib().call_named("amid_scorer_multi_fwd_bwd_f32", u=pl.u.data_ptr(), items=items, w1=pa(fp.ptr(f"{h}.fc.0.weight") for h in heads),
+                         b1=pa(fp.ptr(f"{h}.fc.0.bias") for h in heads), w2=pa(fp.ptr(f"{h}.fc.2.weight") for h in heads),
+                         b2=pa(fp.ptr(f"{h}.fc.2.bias") for h in heads), n_heads=len(heads), labels=pl.labels.data_ptr(), domain_id=pl.domain.data_ptr(),
+                         ob_label=pl.in_ob.data_ptr() if self.dr else None, mode=self.dr_mode if self.dr else 0, dr_e_w=self.dr_e_w, B=shp.B, NI=shp.NI,
+                         D=self.D, hid=self.hid, p1=pa(o[0].data_ptr() for o in outs), p2=pa(o[1].data_ptr() for o in outs),
+                         dp1=pa(o[2].data_ptr() for o in outs), dp2=pa(o[3].data_ptr() for o in outs), loss_part=pl.loss_part.data_ptr(),
+                         dr_loss_part=pl.dr_loss_part.data_ptr() if self.dr else None, du=pl.du.data_ptr(), ditems=ditems,
+                         sc_part=pa(o[4].data_ptr() for o in outs), tr_src=tr_src, tr_dst=tr_dst, n_tr=n_tr, stream=self.s)
 
     def _head_io(self, pl: SasrecPlan, items: int, ditems: int):
         """What the one-launch heads (forward + loss + backward) read and write beside the parameters, under the header's names."""
@@ -1065,7 +1135,6 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         B, T, NI, M = shp.B, shp.Tenc, shp.NI, shp.M
         st = self.step_state.data_ptr()
         tr = 1 if train else 0
-        fp = self.dense
         tr_src, tr_dst, n_tr = self._wT_lists()      # transposed weights: in_proj q/k/v blocks, out_proj, conv1, conv2 for both layers and domains
         # compute = "bf16" on the strip path: the strip backward's data-gradient products take bf16 fragment images of the transposed weights
         # (the fp32 transposes are still refreshed: the row-tile fallbacks and tests read them)
@@ -1110,28 +1179,21 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
                          p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(), dp1=pl.dp1.data_ptr(), dp2=pl.dp2.data_ptr(), B=B, T=T, NI=NI, D=D,
                          hid=self.hid, eps=SASREC_LN_EPS, dx=pl.dxbuf.data_ptr(), ditems=ditems, ln_part=pl.last_part.data_ptr(),
                          sc_part=pl.sc_part.data_ptr(), tr_src=tr_src, tr_dst=tr_dst, n_tr=n_tr, stream=s)
-        def ffn_bwd_args(l):
-            return (pl.tmq.data_ptr(), pl.h[l].data_ptr(), pl.r[l].data_ptr(), self._pp(f"sac{{d}}.forward_layernorms.{l}.weight"),
-                    self._wT(l, 4), self._wT(l, 5), self._wT(l, 3))
+        drop = dict(tmq=pl.tmq.data_ptr(), step_state=st, train=tr, p_drop=SASREC_P_DROP)
 
         lv = self._live_list(pl)
         live_attn = lv is not None and bool(lib().value("amid_attn_live_supported", T, D, self.H, 1))
+        att = dict(d_o=pl.d_o.data_ptr(), B=B, T=T, D=D, H=self.H, causal=1, step_state=st, train=tr, p_drop=SASREC_P_DROP, stream=s)
 
         def attn_bwd(l):
             if live_attn:        # the live sequences only; the others' rows of dq / dk / dv are never read (strip kernels, wgrad hint)
-                L.call("amid_attn_bwd_live_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.o[l].data_ptr(),
-                       pl.stats[l].data_ptr(), pl.d_o.data_ptr(), B, T, D, self.H, 1, l, st, tr, SASREC_P_DROP, pl.dq_l[l].data_ptr(),
-                       pl.dk_l[l].data_ptr(), pl.dv_l[l].data_ptr(), lv, s)
+                L.call_named("amid_attn_bwd_live_f32", self._saved(pl, l), self._grads(pl, l), att, layer=l, live=lv)
                 return
-            L.call("amid_attn_bwd_rows_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.o[l].data_ptr(),
-                   pl.stats[l].data_ptr(), pl.d_o.data_ptr(), None, B, T, D, self.H, 1, l, st, tr, SASREC_P_DROP, pl.dq_l[l].data_ptr(),
-                   pl.dk_l[l].data_ptr(), pl.dv_l[l].data_ptr(), self._own_rows(pl), s)
+            L.call_named("amid_attn_bwd_rows_f32", self._saved(pl, l), self._grads(pl, l), att, layer=l, key_keep=None, row_domain=self._own_rows(pl))
 
         # live: the three row-tile kernels walk the sequences that carry a gradient only (see _own_rows), re-tiled over the CUs
         dom = self._own_rows(pl)
         live = dom is not None and pl.live_rows
-        tm, h1, r1, lnw1, w1T1, w2T1, woT1 = ffn_bwd_args(1)
-        tm, h0, r0, lnw0, w1T0, w2T0, woT0 = ffn_bwd_args(0)
         dx_in = (pl.dx0 if self.inc_bs else pl.dxg).data_ptr()
         seq = bool(pl.strip and lv is not None and live and live_attn and self._seq_backward(pl))
         pl.seq_bwd_used = seq              # (what THIS backward ran: _seq_backward() depends on the step being enqueued; bench.py and tests read this)
@@ -1139,71 +1201,55 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             # the five launches below as one workgroup-long chain per live sequence
             sv = self._seq_ptrs(pl)
             L.call_named("amid_sas_seq_bwd_f32", sv, self._seq_grad_ptrs(pl), self._fams(), self._wT_fams(bf), n_layers=2, dxo=pl.dxbuf.data_ptr(),
-                         tmq=tm, x=sv["x_in"], ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, H=self.H, live=lv, step_state=st, train=tr,
+                         tmq=pl.tmq.data_ptr(), x=sv["x_in"], ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, H=self.H, live=lv, step_state=st, train=tr,
                          p_drop=SASREC_P_DROP, d_o=pl.d_o.data_ptr(), dx=dx_in, mma_bf16=bf, stream=s)
         elif pl.strip:
-            ln1p, ln2p = pl.ln1_part, pl.ln2_part
             # a train step's index sort rides in these three launches (phases 2, 3, 4; phase 1 rode in the catch-up launch)
             riding = getattr(pl, "riding", False)
             sfx = "_sort" if riding else ""
             t2 = getattr(pl, "tail2", False)
             plan_addr = (self._sort_plan_c(pl) if t2 else self._sort_plan(pl)) if riding else None
-            ride = lambda ph: (plan_addr, ph) if riding else ()      # noqa: E731
-            L.call(f"amid_sas_strip_ffn_bwd{sfx}_f32", pl.dxbuf.data_ptr(), tm, h1, r1, lnw1, w1T1, w2T1, woT1, SASREC_LN_EPS, B, T, D, lv, 1, st, tr,
-                   SASREC_P_DROP, pl.dpre2[1].data_ptr(), pl.dpre1[1].data_ptr(), pl.dr[1].data_ptr(), pl.d_o.data_ptr(), ln2p[1].data_ptr(),
-                   *ride(2), self._strip_mode(bf, 0), s)
+            ride = lambda ph: dict(sort_plan=plan_addr, sort_phase=ph) if riding else {}      # noqa: E731
+            strip = dict(ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, live=lv, stream=s)
+            L.call_named(f"amid_sas_strip_ffn_bwd{sfx}_f32", self._ffn_bwd_block(pl, 1, False), strip, drop, ride(2), dxo=pl.dxbuf.data_ptr(),
+                         mma_bf16=self._strip_mode(bf, 0))
             attn_bwd(1)
             # layer 1's q / k / v + LayerNorm1 backward and layer 0's feed-forward / out-projection backward: one launch
+            fused = (self._qkv_bwd_block(pl, 1, False), self._ffn_bwd_block(pl, 0, False, fused=True), strip, drop, ride(3))
             if t2:      # ... whose idle CUs also sum the scorer's weight gradients from the head's per-sample hidden gradients
                 # (a prepared pool: the same launch without the sort's workgroups)
-                mid = ("amid_sas_strip_qkv_bwd_sort_scorer_f32", dict(sort_plan=plan_addr, sort_phase=3)) if riding else ("amid_sas_strip_qkv_bwd_scorer_f32", {})
-                L.call_named(mid[0], self._scorer(("dW1", "db1", "dW2", "db2"), grad=True), **mid[1],
-                             dq=pl.dq_l[1].data_ptr(), dk=pl.dk_l[1].data_ptr(), dv=pl.dv_l[1].data_ptr(), dr=pl.dr[1].data_ptr(),
-                             x=pl.x[1].data_ptr(), ln_w=self._pp("sac{d}.attention_layernorms.1.weight"), wqT=self._wT(1, 0), wkT=self._wT(1, 1),
-                             wvT=self._wT(1, 2), ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, live=lv, ln_part=ln1p[1].data_ptr(), tmq=tm, fh=h0, fr=r0,
-                             fln_w=lnw0, fw1T=w1T0, fw2T=w2T0, fwoT=woT0, flayer=0, step_state=st, train=tr, p_drop=SASREC_P_DROP,
-                             fdpre2=pl.dpre2[0].data_ptr(), fdpre1=pl.dpre1[0].data_ptr(), fdr=pl.dr[0].data_ptr(), fd_o=pl.d_o.data_ptr(),
-                             fln_part=ln2p[0].data_ptr(), mma_bf16=self._strip_mode(bf, 1), hidg=self._hidg(pl).data_ptr(),
-                             u=pl.u.data_ptr(), items=items, NI=NI, hid=self.hid, stream=s)
+                L.call_named(f"amid_sas_strip_qkv_bwd{sfx}_scorer_f32", *fused, self._scorer(("dW1", "db1", "dW2", "db2"), grad=True),
+                             mma_bf16=self._strip_mode(bf, 1), hidg=self._hidg(pl).data_ptr(), u=pl.u.data_ptr(), items=items, NI=NI, hid=self.hid)
             else:
-                L.call(f"amid_sas_strip_qkv_bwd{sfx}_f32", pl.dq_l[1].data_ptr(), pl.dk_l[1].data_ptr(), pl.dv_l[1].data_ptr(), pl.dr[1].data_ptr(),
-                       pl.x[1].data_ptr(), self._pp("sac{d}.attention_layernorms.1.weight"), self._wT(1, 0), self._wT(1, 1), self._wT(1, 2),
-                       SASREC_LN_EPS, B, T, D, lv, None, ln1p[1].data_ptr(), tm, h0, r0, lnw0, w1T0, w2T0, woT0, 0, st, tr, SASREC_P_DROP,
-                       pl.dpre2[0].data_ptr(), pl.dpre1[0].data_ptr(), pl.dr[0].data_ptr(), pl.d_o.data_ptr(), ln2p[0].data_ptr(), *ride(3), self._strip_mode(bf, 1), s)
+                L.call_named(f"amid_sas_strip_qkv_bwd{sfx}_f32", *fused, dx=None, mma_bf16=self._strip_mode(bf, 1))
             attn_bwd(0)
             if t2:      # ... with the embedding layer's backward applied on the strip (no amid_embed_bwd launch)
-                L.call("amid_sas_strip_qkv_bwd_emb_f32", pl.dq_l[0].data_ptr(), pl.dk_l[0].data_ptr(), pl.dv_l[0].data_ptr(), pl.dr[0].data_ptr(),
-                       pl.x[0].data_ptr(), self._pp("sac{d}.attention_layernorms.0.weight"), self._wT(0, 0), self._wT(0, 1), self._wT(0, 2),
-                       SASREC_LN_EPS, B, T, D, lv, dx_in, ln1p[0].data_ptr(), pl.tmq.data_ptr(), st, tr, SASREC_P_DROP, plan_addr, 4 if riding else 0, self._strip_mode(bf, 2), s)
+                L.call_named("amid_sas_strip_qkv_bwd_emb_f32", self._qkv_bwd_block(pl, 0, False), strip, ride(4) if riding else NO_SORT_RIDERS, dx=dx_in,
+                             emb_tmq=pl.tmq.data_ptr(), step_state=st, train=tr, emb_p_drop=SASREC_P_DROP, mma_bf16=self._strip_mode(bf, 2))
             else:
-                L.call(f"amid_sas_strip_qkv_bwd{sfx}_f32", pl.dq_l[0].data_ptr(), pl.dk_l[0].data_ptr(), pl.dv_l[0].data_ptr(), pl.dr[0].data_ptr(),
-                       pl.x[0].data_ptr(), self._pp("sac{d}.attention_layernorms.0.weight"), self._wT(0, 0), self._wT(0, 1), self._wT(0, 2),
-                       SASREC_LN_EPS, B, T, D, lv, dx_in, ln1p[0].data_ptr(), None, None, None, None, None, None, None, 0, None, 0, 0.0, None,
-                       None, None, None, None, *ride(4), self._strip_mode(bf, 2), s)
+                L.call_named(f"amid_sas_strip_qkv_bwd{sfx}_f32", self._qkv_bwd_block(pl, 0, False), NO_FUSED_FFN, strip, ride(4), dx=dx_in,
+                             mma_bf16=self._strip_mode(bf, 2))
         else:
             rows, suf, rpt = ("_rows", pl.rt_suffix_v, pl.rpt_v) if live else ("", pl.rt_suffix, pl.rpt)
-            ln1p, ln2p = (pl.ln1_part_v, pl.ln2_part_v) if live else (pl.ln1_part, pl.ln2_part)
-            hint = (dom, B, T) if live else ()
-            L.call(f"amid_sas_ffn_bwd{rows}_f32" + suf, pl.dxbuf.data_ptr(), tm, h1, r1, lnw1, w1T1, w2T1, woT1, SASREC_LN_EPS, M, D, rpt, 1, st, tr,
-                   SASREC_P_DROP, pl.dpre2[1].data_ptr(), pl.dpre1[1].data_ptr(), pl.dr[1].data_ptr(), pl.d_o.data_ptr(),
-                   ln2p[1].data_ptr(), self.mma_bf16, *hint, s)
+            hint = dict(row_domain=dom, B=B, T=T) if live else {}
+            tile = dict(ln_eps=SASREC_LN_EPS, M=M, D=D, rows_per_tile=rpt, mma_bf16=self.mma_bf16, stream=s)
+            L.call_named(f"amid_sas_ffn_bwd{rows}_f32" + suf, self._ffn_bwd_block(pl, 1, live), tile, drop, hint, dxo=pl.dxbuf.data_ptr())
             attn_bwd(1)
             # layer 1's q / k / v + LayerNorm1 backward and layer 0's feed-forward / out-projection backward: one launch
-            L.call(f"amid_sas_qkv_ffn_bwd{rows}_f32" + suf, pl.dq_l[1].data_ptr(), pl.dk_l[1].data_ptr(), pl.dv_l[1].data_ptr(), pl.dr[1].data_ptr(),
-                   pl.x[1].data_ptr(), self._pp("sac{d}.attention_layernorms.1.weight"), self._wT(1, 0), self._wT(1, 1), self._wT(1, 2),
-                   SASREC_LN_EPS, M, D, rpt, pl.dxbuf.data_ptr(), ln1p[1].data_ptr(), tm, h0, r0, lnw0, w1T0, w2T0, woT0, 0, st, tr,
-                   SASREC_P_DROP, pl.dpre2[0].data_ptr(), pl.dpre1[0].data_ptr(), pl.dr[0].data_ptr(), pl.d_o.data_ptr(),
-                   ln2p[0].data_ptr(), self.mma_bf16, *hint, s)
+            L.call_named(f"amid_sas_qkv_ffn_bwd{rows}_f32" + suf, self._qkv_bwd_block(pl, 1, live), self._ffn_bwd_block(pl, 0, live, fused=True), tile, drop, hint,
+                         dx=pl.dxbuf.data_ptr())
             attn_bwd(0)
-            L.call(f"amid_sas_qkv_bwd{rows}_f32" + suf, pl.dq_l[0].data_ptr(), pl.dk_l[0].data_ptr(), pl.dv_l[0].data_ptr(), pl.dr[0].data_ptr(),
-                   pl.x[0].data_ptr(), self._pp("sac{d}.attention_layernorms.0.weight"), self._wT(0, 0), self._wT(0, 1), self._wT(0, 2),
-                   SASREC_LN_EPS, M, D, rpt, dx_in, ln1p[0].data_ptr(), self.mma_bf16, *hint, s)
+            L.call_named(f"amid_sas_qkv_bwd{rows}_f32" + suf, self._qkv_bwd_block(pl, 0, live), tile, hint, dx=dx_in)
         dy, xx = [], []
         for l in (0, 1):
             dy += [pl.dq_l[l].data_ptr(), pl.dk_l[l].data_ptr(), pl.dv_l[l].data_ptr(), pl.dr[l].data_ptr(), pl.dpre1[l].data_ptr(),
                    pl.dpre2[l].data_ptr()]
             xx += [pl.qn[l].data_ptr(), pl.x[l].data_ptr(), pl.x[l].data_ptr(), pl.o[l].data_ptr(), pl.y[l].data_ptr(), pl.h[l].data_ptr()]
         # NOTE: pl.x[0] is the gathered-row buffer xg, still intact here (its gradient lives in dxg)
+        wgrad = lambda: dict(self._on_plan(pl, "wgrad_tab", lambda: dict(      # noqa: E731  (dy, x: read when the launch is enqueued)
+            n_layers=2, M=M, D=D, splits=pl.splits, w_part=ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]),
+            b_part=ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]), B=B, T=T)), dy=ptr_array(dy), x=ptr_array(xx),
+            row_domain=self._own_rows(pl), stream=s)
         t2 = bool(getattr(pl, "tail2", False) and pl.strip and not seq)
         if t2:      # the last phase of the step's index sort (run heads) rides in the weight gradients; the embedding backward is done
             if getattr(pl, "lnstat_fwd", False):      # the forward stored row statistics instead of qn / y: the operands of q's and conv1's
@@ -1215,33 +1261,23 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
                 finally:
                     self._wgrad_one = False
                 # (of the families it takes the four LayerNorm ones; a prepared pool: no rider z-slice)
-                wg = ("amid_sas_wgrad_rows_sort_ln_f32", dict(sort_plan=self._sort_plan_c(pl))) if pl.riding else ("amid_sas_wgrad_rows_ln_f32", {})
-                L.call_named(wg[0], self._fams(), dy=ptr_array(dy), x=ptr_array(xx), n_layers=2, M=M, D=D,
-                             splits=pl.splits, w_part=ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]),
-                             b_part=ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]), row_domain=self._own_rows(pl), B=B, T=T,
-                             mma_bf16=wmode, ln_stat=self._ln_stat(pl)[1], stream=s, **wg[1])
+                L.call_named("amid_sas_wgrad_rows_sort_ln_f32" if pl.riding else "amid_sas_wgrad_rows_ln_f32", self._fams(), wgrad(),
+                             dict(sort_plan=self._sort_plan_c(pl)) if pl.riding else {}, mma_bf16=wmode, ln_stat=self._ln_stat(pl)[1])
             elif not pl.riding:
-                L.call("amid_sas_wgrad_rows_f32", ptr_array(dy), ptr_array(xx), 2, M, D, pl.splits,
-                       ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]), ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]),
-                       self._own_rows(pl), B, T, self._wgrad_mode(D), s)
+                L.call_named("amid_sas_wgrad_rows_f32", wgrad(), mma_bf16=self._wgrad_mode(D))
             else:
-                L.call("amid_sas_wgrad_rows_sort_f32", ptr_array(dy), ptr_array(xx), 2, M, D, pl.splits,
-                       ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]), ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]),
-                       self._own_rows(pl), B, T, self._wgrad_mode(D), self._sort_plan_c(pl), s)
+                L.call_named("amid_sas_wgrad_rows_sort_f32", wgrad(), mma_bf16=self._wgrad_mode(D), sort_plan=self._sort_plan_c(pl))
             self._enqueue_grad_tail(pl, live, seq)
             return
-        L.call("amid_sas_wgrad_rows_f32", ptr_array(dy), ptr_array(xx), 2, M, D, pl.splits, ptr_array([pl.w_part[0].data_ptr(), pl.w_part[1].data_ptr()]),
-               ptr_array([pl.b_part[0].data_ptr(), pl.b_part[1].data_ptr()]), self._own_rows(pl), B, T,
-               self._wgrad_mode(D), s)
+        L.call_named("amid_sas_wgrad_rows_f32", wgrad(), mma_bf16=self._wgrad_mode(D))
+        emb = dict(dxg=dx_in, tmq=pl.tmq.data_ptr(), B=B, T=T, D=D, nsplit=pl.pos_splits, dpos_part=pl.dpos_part.data_ptr(), step_state=st,
+                   train=tr, p_drop=SASREC_P_DROP, stream=s)
         if getattr(pl, "riding", False):     # the last phase of the step's index sort (run heads) rides here
-            L.call("amid_embed_bwd_sort_f32", (pl.dx0 if self.inc_bs else pl.dxg).data_ptr(), pl.tmq.data_ptr(), B, T, D, pl.pos_splits,
-                   pl.dpos_part.data_ptr(), st, tr, SASREC_P_DROP, dom if live else None, self._sort_plan(pl), 5, s)
+            L.call_named("amid_embed_bwd_sort_f32", emb, row_domain=dom if live else None, sort_plan=self._sort_plan(pl), sort_phase=5)
         elif live:     # the dead sequences' rows of the encoder-input gradient were never written: zero-filled here, not read
-            L.call("amid_embed_bwd_rows_f32", (pl.dx0 if self.inc_bs else pl.dxg).data_ptr(), pl.tmq.data_ptr(), B, T, D, pl.pos_splits,
-                   pl.dpos_part.data_ptr(), st, tr, SASREC_P_DROP, dom, s)
+            L.call_named("amid_embed_bwd_rows_f32", emb, row_domain=dom)
         else:
-            L.call("amid_embed_bwd_f32", (pl.dx0 if self.inc_bs else pl.dxg).data_ptr(), pl.tmq.data_ptr(), B, T, D, pl.pos_splits,
-                   pl.dpos_part.data_ptr(), st, tr, SASREC_P_DROP, s)
+            L.call_named("amid_embed_bwd_f32", emb)
         if self.inc_bs:      # InnerComp's parameter gradients; the rows' own halves + its share -> the table-row gradient buffer
             G = self.dense.grad
             head = (pl.dpos_part.data_ptr(), pl.pos_splits, pl.xg.data_ptr(), pl.dx0.data_ptr(), pl.inc_gate.data_ptr(), pl.inc_S.data_ptr(),
@@ -1276,72 +1312,47 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
                                else (pl.red_entries, pl.red_n, pl.red_max))
         pk = getattr(self, "_tail_pack", None)
         pl.spans_done = False
+        seg = self._seg(pl)
+        if pk is not None:       # graph A of the data-parallel step: the reduced rows go into this rank's exchange chunk, packed by the tail
+            seg = dict(seg, **self._pack_block(pl, pk))
+        red = lambda e, n, b: dict(entries_dev=e.data_ptr(), n_entries=n, blk_off=b[0].data_ptr(), total_blocks=b[1])      # noqa: E731
+        pos_rows = lambda: dict(self._dpos(), live=pl.live.data_ptr(), B=shp.B, T=shp.Tenc)      # noqa: E731  (the folded tails sum the position rows' gradients)
         if getattr(pl, "tail2", False) and not getattr(self, "_in_train_step", False):
             # the folded step under data parallel: the exchange ships finished rows, so phase B of the segment reduce is a launch of its own
             # behind the tail -- and in graph A of the graph pair the packing of this rank's chunk (ids | rows | dense) rides in it
-            ent_t, n_ent_t, blk_t = self._tail2_table(pl)
             fp = self.dense
-            head = (pl.dxg.data_ptr(), pl.pos_sorted.data_ptr(), pl.seg_off.data_ptr(), pl.seg_of.data_ptr(), pl.n_compact, self.D,
-                    pl.seg_ws.data_ptr())
-            mid = (ent_t.data_ptr(), n_ent_t, blk_t[0].data_ptr(), blk_t[1], pl.live.data_ptr(), shp.B, shp.Tenc,
-                   fp.ptr("sac1.pos_emb.weight", fp.grad), fp.ptr("sac2.pos_emb.weight", fp.grad))
+            tail = (red(*self._tail2_table(pl)), pos_rows(), dict(n_idx=pl.n_compact, D=self.D, stream=s))
             if self.FUSED_OPT:        # ... all of it as ONE launch (amid_grad_tail_opt_f32's workgroups, shipping instead of applying)
                 left_lo = fp.slots["predictModule.fc.0.weight"][0]      # the scorer's gradients: final before this launch (the strip riders)
-                dense = (fp.grad.data_ptr(), fp.numel, left_lo, fp.numel, pl.uniq_ids.data_ptr(), pl.n_uniq.data_ptr(), pl.n_compact)
+                dense = (self._adam_dense(), self._uniq(pl), dict(left_lo=left_lo, left_hi=fp.numel, n_uniq_max=pl.n_compact,
+                                                                  ticket=pl.tail_ticket.data_ptr()))
                 if pk is not None:
-                    from .dist import packed_rows
-                    send, umax, with_dense = pk
-                    id_rows, rows = packed_rows(umax, self.D)
-                    L.call("amid_grad_tail_live_dp1_f32", *head, send.data_ptr() + 4 * id_rows * self.D, *mid, *dense, umax, self.n_rows,
-                           send.data_ptr(), send.data_ptr() + 4 * rows * self.D if with_dense else None, pl.err.data_ptr(),
-                           pl.tail_ticket.data_ptr(), s)
+                    L.call_named("amid_grad_tail_live_dp1_f32", seg, *tail, *dense)
                 else:
-                    L.call("amid_grad_tail_live_dp1_f32", *head, pl.uniq_grad.data_ptr(), *mid, *dense, 0, 0, None, None, None,
-                           pl.tail_ticket.data_ptr(), s)
+                    L.call_named("amid_grad_tail_live_dp1_f32", seg, NO_PACK, *tail, *dense)
             elif pk is not None:
-                from .dist import packed_rows
-                send, umax, with_dense = pk
-                id_rows, rows = packed_rows(umax, self.D)
-                L.call("amid_grad_tail_live_dp_f32", *head, send.data_ptr() + 4 * id_rows * self.D, *mid, pl.uniq_ids.data_ptr(),
-                       pl.n_uniq.data_ptr(), umax, self.n_rows, send.data_ptr(), self.dense.grad.data_ptr() if with_dense else None,
-                       send.data_ptr() + 4 * rows * self.D if with_dense else None, self.dense.numel if with_dense else 0,
-                       pl.err.data_ptr(), s)
+                L.call_named("amid_grad_tail_live_dp_f32", seg, self._uniq(pl), *tail)
             else:
-                L.call("amid_grad_tail_live_dp_f32", *head, pl.uniq_grad.data_ptr(), *mid, None, None, 0, 0, None, None, None, 0, None, s)
+                L.call_named("amid_grad_tail_live_dp_f32", seg, NO_PACK, NO_UNIQ, *tail)
             pl.spans_done = True
             return
         pl.opt_done = False
+        opt = dict(grad_scale=self.grad_scale, step_state=self.step_state.data_ptr(), ticket=pl.tail_ticket.data_ptr(), D=self.D, stream=s)
         if getattr(pl, "tail2", False) and self.FUSED_OPT and self.table_m is not None and not self.dr:
             # the folded step's tail AND its optimizer as one launch (round 6): every producer of a gradient slice applies Adam on the spot
-            ent_t, n_ent_t, blk_t = self._tail2_table(pl)
             fp = self.dense
             left_lo = fp.slots["predictModule.fc.0.weight"][0]          # the scorer's slots (the flat buffer's tail): summed by the strip riders
-            L.call("amid_grad_tail_opt_f32", pl.dxg.data_ptr(), pl.pos_sorted.data_ptr(), pl.seg_off.data_ptr(), pl.seg_of.data_ptr(), pl.n_compact,
-                   self.D, pl.seg_ws.data_ptr(), pl.uniq_grad.data_ptr(), ent_t.data_ptr(), n_ent_t, blk_t[0].data_ptr(), blk_t[1],
-                   pl.live.data_ptr(), shp.B, shp.Tenc, fp.ptr("sac1.pos_emb.weight", fp.grad), fp.ptr("sac2.pos_emb.weight", fp.grad),
-                   fp.data.data_ptr(), fp.m.data_ptr(), fp.v.data_ptr(), fp.grad.data_ptr(), fp.numel, left_lo, fp.numel,
-                   self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(), pl.uniq_ids.data_ptr(),
-                   pl.n_uniq.data_ptr(), pl.n_compact, self.grad_scale, self.step_state.data_ptr(), pl.tail_ticket.data_ptr(), s)
+            L.call_named("amid_grad_tail_opt_f32", seg, red(*self._tail2_table(pl)), pos_rows(), self._adam_dense(), self._adam_rows(), self._uniq(pl),
+                         opt, n_idx=pl.n_compact, left_lo=left_lo, left_hi=fp.numel, n_uniq_max=pl.n_compact)
             pl.opt_done = True
             return
         if getattr(pl, "tail2", False):
-            ent_t, n_ent_t, blk_t = self._tail2_table(pl)
-            fp = self.dense
-            L.call("amid_grad_tail_live_f32", pl.dxg.data_ptr(), pl.pos_sorted.data_ptr(), pl.seg_off.data_ptr(), pl.seg_of.data_ptr(), pl.n_compact,
-                   self.D, pl.seg_ws.data_ptr(), pl.uniq_grad.data_ptr(), ent_t.data_ptr(), n_ent_t, blk_t[0].data_ptr(), blk_t[1],
-                   pl.live.data_ptr(), shp.B, shp.Tenc, fp.ptr("sac1.pos_emb.weight", fp.grad), fp.ptr("sac2.pos_emb.weight", fp.grad),
-                   None, None, None, 0, 0, None, None, None, None, s)      # (the scorer sums rode in the middle strip launch)
+            L.call_named("amid_grad_tail_live_f32", seg, red(*self._tail2_table(pl)), pos_rows(), NO_SCORER_SUMS,      # (the scorer sums rode in the
+                         n_idx=pl.n_compact, D=self.D, stream=s)                                                     # middle strip launch)
             return
         if pk is not None:       # graph A of the data-parallel step: the tail also packs this rank's exchange chunk (ids | rows | dense)
-            from .dist import packed_rows
-            send, umax, with_dense = pk
-            id_rows, rows = packed_rows(umax, self.D)
-            L.call("amid_grad_tail_pack_f32", pl.dxg.data_ptr(), pl.pos_sorted.data_ptr(), pl.seg_off.data_ptr(), pl.seg_of.data_ptr(), self.n_sparse(pl),
-                   self.D, pl.seg_ws.data_ptr(), send.data_ptr() + 4 * id_rows * self.D, ent.data_ptr(),
-                   n_ent, ent_max, pl.uniq_ids.data_ptr(), pl.n_uniq.data_ptr(), umax,
-                   self.n_rows, send.data_ptr(), self.dense.grad.data_ptr() if with_dense else None,
-                   send.data_ptr() + 4 * rows * self.D if with_dense else None, self.dense.numel if with_dense else 0,
-                   pl.err.data_ptr(), blk[0].data_ptr(), blk[1], s)
+            L.call_named("amid_grad_tail_pack_f32", seg, red(ent, n_ent, blk), self._uniq(pl), max_count=ent_max, n_idx=self.n_sparse(pl), D=self.D,
+                         stream=s)
             return
         # a single-GPU train step's optimizer launch follows: it finishes the runs that cross chunks itself (amid_optimizer_step_spans_f32;
         # the same additions in the same order as the spans launch this saves).  Not for enqueue_local_grads: the exchange ships uniq_grad
@@ -1350,30 +1361,36 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         if spans_later and self.FUSED_OPT and self.table_m is not None and left is not None:
             # ... and the optimizer itself: the tail's workgroups apply Adam to every slice they finish (amid_grad_tail_opt_f32 without its
             # position-row role: here every dense gradient is an entry of the reduce table) -- one launch fewer in every single-GPU step
-            fp = self.dense
-            L.call("amid_grad_tail_opt_f32", pl.dxg.data_ptr(), pl.pos_sorted.data_ptr(), pl.seg_off.data_ptr(), pl.seg_of.data_ptr(), self.n_sparse(pl),
-                   self.D, pl.seg_ws.data_ptr(), pl.uniq_grad.data_ptr(), ent.data_ptr(), n_ent, blk[0].data_ptr(), blk[1],
-                   None, 0, 0, None, None, fp.data.data_ptr(), fp.m.data_ptr(), fp.v.data_ptr(), fp.grad.data_ptr(), fp.numel, *(left or (0, 0)),
-                   self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(), pl.uniq_ids.data_ptr(),
-                   pl.n_uniq.data_ptr(), self.n_sparse(pl), self.grad_scale, self.step_state.data_ptr(), pl.tail_ticket.data_ptr(), s)
+            left_lo, left_hi = left or (0, 0)
+            L.call_named("amid_grad_tail_opt_f32", seg, red(ent, n_ent, blk), NO_POS_ROWS, self._adam_dense(), self._adam_rows(), self._uniq(pl),
+                         opt, n_idx=self.n_sparse(pl), left_lo=left_lo, left_hi=left_hi, n_uniq_max=self.n_sparse(pl))
             pl.opt_done = True
             return
         pl.spans_owed = self.n_sparse(pl) if spans_later else 0
-        L.call("amid_grad_tail_nospans_f32" if spans_later else "amid_grad_tail_f32", pl.dxg.data_ptr(), pl.pos_sorted.data_ptr(), pl.seg_off.data_ptr(),
-               pl.seg_of.data_ptr(), self.n_sparse(pl), self.D, pl.seg_ws.data_ptr(), pl.uniq_grad.data_ptr(), ent.data_ptr(), n_ent, ent_max,
-               blk[0].data_ptr(), blk[1], s)
+        L.call_named("amid_grad_tail_nospans_f32" if spans_later else "amid_grad_tail_f32", seg, red(ent, n_ent, blk), max_count=ent_max,
+                     n_idx=self.n_sparse(pl), D=self.D, stream=s)
+
+    def _pack_block(self, pl: SasrecPlan, pk):
+        """The packing a gradient tail does for graph A of the data-parallel step, from _tail_pack = (this rank's chunk, its bound, whether
+        the dense gradient travels in it): the chunk is ids | rows | dense, so the REDUCED ROWS (uniq_grad) land behind its ids."""
+        from .dist import packed_rows
+        send, umax, with_dense = pk
+        id_rows, rows = packed_rows(umax, self.D)
+        return dict(uniq_grad=send.data_ptr() + 4 * id_rows * self.D, n_out=umax, pad_id=self.n_rows, out_ids=send.data_ptr(),
+                    dense_src=self.dense.grad.data_ptr() if with_dense else None,
+                    dense_dst=send.data_ptr() + 4 * rows * self.D if with_dense else None, dense_n=self.dense.numel if with_dense else 0,
+                    err_flag=pl.err.data_ptr())
 
     def enqueue_optimizer(self, pl: SasrecPlan, sparse=None) -> None:
         """Dense Adam on the flat buffer + lazy row Adam on (uniq_ids, uniq_grad, n_uniq); `sparse`
         overrides the plan's local lists with the world-merged ones under data parallelism."""
         L, s = lib(), self.s
         self._ensure_opt_state()
-        fp = self.dense
         if sparse is None:
-            ids, rows, nu, cap = pl.uniq_ids, pl.uniq_grad, pl.n_uniq, self.n_sparse(pl)
+            lists, cap = (self._uniq(pl), self._seg(pl)), self.n_sparse(pl)
         else:
             ids, rows, nu = sparse
-            cap = ids.numel()
+            lists, cap = (dict(uniq_ids=ids.data_ptr(), n_uniq=nu.data_ptr(), uniq_grad=rows.data_ptr()),), ids.numel()
         if getattr(pl, "opt_done", False):          # the gradient tail applied the step (amid_grad_tail_opt_f32)
             pl.opt_done = False
             if sparse is not None:
@@ -1382,17 +1399,14 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         owed = int(getattr(pl, "spans_owed", 0))
         pl.spans_owed = 0
         t2 = getattr(pl, "tail2", False) and not getattr(pl, "spans_done", False)
+        adam = (self._adam_dense(), self._adam_rows(), dict(n_uniq_max=cap, D=self.D, grad_scale=self.grad_scale,
+                                                            step_state=self.step_state.data_ptr(), stream=s))
         if sparse is None and (t2 or owed):      # the segment reduce's runs across chunks are finished (and applied) here
-            L.call("amid_optimizer_step_spans_f32", fp.data.data_ptr(), fp.m.data_ptr(), fp.v.data_ptr(), fp.grad.data_ptr(), fp.numel,
-                   self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(), ids.data_ptr(),
-                   nu.data_ptr(), cap, rows.data_ptr(), self.D, self.grad_scale, self.step_state.data_ptr(), pl.seg_off.data_ptr(),
-                   pl.seg_of.data_ptr(), pl.n_compact if t2 else owed, pl.seg_ws.data_ptr(), s)
+            L.call_named("amid_optimizer_step_spans_f32", *adam, *lists, n_sorted=pl.n_compact if t2 else owed)
             return
         if owed:
             raise RuntimeError("the gradient tail left the chunk-crossing runs to an optimizer launch that takes merged lists")
-        L.call("amid_optimizer_step_f32", fp.data.data_ptr(), fp.m.data_ptr(), fp.v.data_ptr(), fp.grad.data_ptr(), fp.numel,
-               self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(), ids.data_ptr(),
-               nu.data_ptr(), cap, rows.data_ptr(), self.D, self.grad_scale, self.step_state.data_ptr(), s)
+        L.call_named("amid_optimizer_step_f32", *adam, *lists)
 
     def enqueue_loop_optimizer(self, pl: SasrecPlan, g: torch.Tensor, sqnorm: Optional[torch.Tensor] = None, max_norm: float = float("inf")) -> None:
         """The optimizer launch of the reference's own loop (amid_amd/optim.py): enqueue_optimizer's plain form reading the dense gradient
@@ -1401,14 +1415,12 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         self._ensure_opt_state()
         if getattr(pl, "opt_done", False) or int(getattr(pl, "spans_owed", 0)):
             raise RuntimeError("the plan's last backward was a fused train step's: its gradients are applied already")
-        fp = self.dense
-        args = (fp.data.data_ptr(), fp.m.data_ptr(), fp.v.data_ptr(), g.data_ptr(), fp.numel, self.table.data_ptr(), self.table_m.data_ptr(),
-                self.table_v.data_ptr(), self.table_last.data_ptr(), pl.uniq_ids.data_ptr(), pl.n_uniq.data_ptr(), self.n_sparse(pl),
-                pl.uniq_grad.data_ptr(), self.D, self.grad_scale, self.step_state.data_ptr())
+        adam = (self._adam_dense(g), self._adam_rows(), self._uniq(pl), self._seg(pl),
+                dict(n_uniq_max=self.n_sparse(pl), D=self.D, grad_scale=self.grad_scale, step_state=self.step_state.data_ptr(), stream=self.s))
         if sqnorm is None:
-            lib().call("amid_optimizer_step_f32", *args, self.s)
+            lib().call_named("amid_optimizer_step_f32", *adam)
         else:
-            lib().call("amid_optimizer_step_clip_f32", *args, sqnorm.data_ptr(), float(max_norm), self.s)
+            lib().call_named("amid_optimizer_step_clip_f32", *adam, sqnorm=sqnorm.data_ptr(), max_norm=float(max_norm))
 
     def enqueue_grad_sqnorm(self, pl: SasrecPlan, g: torch.Tensor, out: torch.Tensor) -> None:
         """out[0] = the squared 2-norm of the whole model's gradient: the flat dense gradient `g` and the plan's unique table rows."""
@@ -1550,8 +1562,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         L, s, shp, D = lib(), self.s, pl.shape, self.D
         B, T, NI = shp.B, shp.Tenc, shp.NI
         self._eval_out(pl)
-        L.call("amid_pack_indices_live", pl.in_i_node.data_ptr(), pl.in_neg.data_ptr(), pl.in_seq_d1.data_ptr(), pl.in_seq_d2.data_ptr(),
-               B, shp.T, NI - 1, self.n_rows, pl.idx_all.data_ptr(), pl.err.data_ptr(), None, pl.domain.data_ptr(), pl.live.data_ptr(), s)
+        L.call_named("amid_pack_indices_live", self._marshal(pl), step_state=None, stream=s)
         if self._eval_through_forward():           # enqueue_forward's launches up to the last encoder layer, the sequences' rows only
             self.enqueue_forward(pl, train=False, with_loss=False, head=False, gather_items=False)
         else:
@@ -1594,7 +1605,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         inference twins (tests/test_gpu_eval.py)."""
         L, s, shp, D = lib(), self.s, pl.shape, self.D
         B, T = shp.B, shp.Tenc
-        fp, st = self.dense, self.step_state.data_ptr()
+        st = self.step_state.data_ptr()
         lf = None if self.itc_bs else pl.live.data_ptr()      # isItC: the pair-max reads both domains' rows of every sample
         pos = self._pos()
         if not L.value("amid_sas_seq_supported", B, T, D, self.H):       # eval_fused_ok said yes: the long shape (_eval_long)
@@ -1604,23 +1615,21 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         pl.w16_written = pl.wT16x3_written = False
         # the forward's workgroups gather their own rows: three launches a batch (the gather prologue walks a live list: not without one)
         gat = bool(split and self.GATHER_ON_FWD and lf is not None)
+        k1 = self._k1_head(pl, pos["pos0"], pos["pos1"], pl.tmq.data_ptr(), 0, SASREC_P_DROP, 0)      # (no candidate rows: the head gathers them)
         if gat:
             src, w16 = self._w16_images(3)
             if build_images:
                 L.call("amid_sas_weights_bf16_planes", src, 24, D, 0, 3, w16.data_ptr(), s)
         elif split and build_images:          # the gather's extra workgroups write the weights' three-plane images (the forward's operands)
             src, w16 = self._w16_images(3)
-            L.call("amid_embed_fwd_w16_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos["pos0"], pos["pos1"], B, T, D, 0, pl.xg.data_ptr(), pl.tmq.data_ptr(),
-                   st, 0, SASREC_P_DROP, lf, None, None, src, 24, 3, w16.data_ptr(), None, s)
+            L.call_named("amid_embed_fwd_w16_f32", k1, self._w16_riders(transposes=False), table=self.table.data_ptr(), live=lf, idx_c=None, row_c=None)
         else:
             if split:
                 src, w16 = self._w16_images(3)
             if lf is not None:
-                L.call("amid_embed_fwd_live_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos["pos0"], pos["pos1"], B, T, D, 0, pl.xg.data_ptr(),
-                       pl.tmq.data_ptr(), st, 0, SASREC_P_DROP, lf, s)
+                L.call_named("amid_embed_fwd_live_f32", k1, table=self.table.data_ptr(), live=lf)
             else:
-                L.call("amid_embed_fwd_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), pos["pos0"], pos["pos1"], B, T, D, 0, pl.xg.data_ptr(), pl.tmq.data_ptr(),
-                       st, 0, SASREC_P_DROP, s)
+                L.call_named("amid_embed_fwd_f32", k1, table=self.table.data_ptr())
         fams = self._fams()
         enc = dict(n_layers=2, xout=pl.x[2].data_ptr(), ln_eps=SASREC_LN_EPS, B=B, T=T, D=D, H=self.H, live=lf, stream=s)
         if gat:
@@ -1643,16 +1652,12 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         L, s, shp, D = lib(), self.s, pl.shape, self.D
         lay = self._lay()
         dims = dict(B=shp.B, T=shp.Tenc, D=D, live=lf, stream=s)
-        out = lambda l, pre="": {pre + n: getattr(pl, n)[l].data_ptr() for n in ("qn", "q", "k", "v")}      # noqa: E731
-        # (a layer's table under its q / k / v launch's names; under the next layer's, n..., in the launch in front of it)
-        qkv = lambda l, pre="": dict(out(l, pre), **{pre + "ln_w": lay[l]["ln1_w"], pre + "ln_b": lay[l]["ln1_b"],      # noqa: E731
-                                                     pre + "w_in": lay[l]["w_in"], pre + "b_in": lay[l]["b_in"]})
-        L.call_named("amid_sas_strip_qkv_fwd_gather_infer_f32", pos, qkv(0), dims, table=self.table.data_ptr(), idx_all=pl.idx_all.data_ptr(),
+        L.call_named("amid_sas_strip_qkv_fwd_gather_infer_f32", pos, self._qkv_block(pl, 0), dims, table=self.table.data_ptr(), idx_all=pl.idx_all.data_ptr(),
                      ln_eps=SASREC_LN_EPS, tmq=pl.tmq.data_ptr())
         for l in (0, 1):
             L.call_named("amid_attn_fwd_long_live_infer_f32", dims, q=pl.q[l].data_ptr(), k=pl.k[l].data_ptr(), v=pl.v[l].data_ptr(), H=self.H,
                          o=pl.o[l].data_ptr())
-            nxt = qkv(1, "n") if l == 0 else dict.fromkeys(qkv(1, "n"))
+            nxt = self._qkv_block(pl, 1, "n") if l == 0 else NO_NEXT_QKV
             L.call_named("amid_sas_strip_oproj_ffn_fwd_infer_f32", lay[l], nxt, dims, o=pl.o[l].data_ptr(), qn=pl.qn[l].data_ptr(),
                          ln_w=lay[l]["ln2_w"], ln_b=lay[l]["ln2_b"], tmq=pl.tmq.data_ptr(), ln_eps=SASREC_LN_EPS,
                          xo=None if l == 0 else pl.x[2].data_ptr())
@@ -1738,11 +1743,18 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         B = pl.shape.B
         p1, p2 = pools
         ws = self._full_rank_workspace(B, p1.numel(), p2.numel(), 0)
+        lib().call_named("amid_full_rank_f32", self._scorer(), self._catalog(domain, pools, own, own_off, rows), u=u.data_ptr(), u_dom_stride=stride,
+                         pos=pos.data_ptr(), B=B, fix_value=float(fix_value), workspace=ws.data_ptr(), flags=pl.err.data_ptr(), rank=rank.data_ptr(),
+                         rank_raw=rank_raw.data_ptr(), scores=None if scores is None else scores.data_ptr(),
+                         n_cols=0 if scores is None else scores.shape[1])
+
+    def _catalog(self, domain: torch.Tensor, pools, own, own_off, rows):
+        """What the full-catalog launches score against: the rows' domains, the two pools, the rows' own items (or None), the table."""
         ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
-        lib().call("amid_full_rank_f32", u.data_ptr(), stride, pos.data_ptr(), domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(),
-                   p2.numel(), ptr(own), ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer().values(), self.D, self.hid,
-                   float(fix_value), ws.data_ptr(), pl.err.data_ptr(), rank.data_ptr(), rank_raw.data_ptr(), ptr(scores),
-                   0 if scores is None else scores.shape[1], self.s)
+        p1, p2 = pools
+        return dict(domain_id=domain.data_ptr(), pool_d1=p1.data_ptr(), n_pool_d1=p1.numel(), pool_d2=p2.data_ptr(), n_pool_d2=p2.numel(),
+                    own_items=ptr(own), own_off=ptr(own_off), rows=ptr(rows), table=self.table.data_ptr(), n_rows=self.n_rows, D=self.D,
+                    hid=self.hid, stream=self.s)
 
     def enqueue_topk(self, pl: SasrecPlan, domain: torch.Tensor, pools, own: Optional[torch.Tensor], own_off: Optional[torch.Tensor],
                      rows: Optional[torch.Tensor], k: int, exclude_history: bool, ids: torch.Tensor, scores: torch.Tensor) -> None:
@@ -1752,10 +1764,9 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         B = pl.shape.B
         p1, p2 = pools
         ws = self._full_rank_workspace(B, p1.numel(), p2.numel(), int(k))
-        ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
-        lib().call("amid_topk_f32", u.data_ptr(), stride, domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel(), ptr(own),
-                   ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer().values(), self.D, self.hid, int(k),
-                   1 if exclude_history else 0, ws.data_ptr(), pl.err.data_ptr(), ids.data_ptr(), scores.data_ptr(), self.s)
+        lib().call_named("amid_topk_f32", self._scorer(), self._catalog(domain, pools, own, own_off, rows), u=u.data_ptr(), u_dom_stride=stride, B=B,
+                         top_k=int(k), exclude_history=1 if exclude_history else 0, workspace=ws.data_ptr(), flags=pl.err.data_ptr(), ids=ids.data_ptr(),
+                         scores=scores.data_ptr())
 
     # ------------------------------------------------------------------ the encode / score split and neighbours (csrc/neighbors.hip)
     def encode_epoch(self, pl: SasrecPlan, packed: torch.Tensor, use_graph: bool = True) -> torch.Tensor:
@@ -1819,10 +1830,9 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
                 rows = torch.arange(B, dtype=torch.int32, device=self.device)
             L.call("amid_own_from_seq_i64", history.data_ptr(), history.data_ptr(), domain.data_ptr(), B, T, cnt.data_ptr(), own.data_ptr(),
                    own_off.data_ptr(), self.s)
-        ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
-        L.call("amid_topk_f32", u.data_ptr(), 0, domain.data_ptr(), B, p1.data_ptr(), p1.numel(), p2.data_ptr(), p2.numel(), ptr(own),
-               ptr(own_off), ptr(rows), self.table.data_ptr(), self.n_rows, *self._scorer().values(), self.D, self.hid, int(k),
-               0 if history is None else 1, ws.data_ptr(), err.data_ptr(), ids.data_ptr(), scores.data_ptr(), self.s)
+        L.call_named("amid_topk_f32", self._scorer(), self._catalog(domain, pools, own, own_off, rows), u=u.data_ptr(), u_dom_stride=0, B=B, top_k=int(k),
+                     exclude_history=0 if history is None else 1, workspace=ws.data_ptr(), flags=err.data_ptr(), ids=ids.data_ptr(),
+                     scores=scores.data_ptr())
 
     NEIGHBOR_METRICS = {"dot": 0, "cosine": 1}
 

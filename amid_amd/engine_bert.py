@@ -13,7 +13,7 @@ from typing import List, Tuple
 
 import torch
 
-from ._lib import lib, ptr_array
+from ._lib import absent, lib, prefixed, ptr_array
 from .engine import SasrecEngine, SasrecPlan
 
 BERT_HEADS, BERT_FF, BERT_P_DROP, BERT_HIDDEN = 4, 512, 0.1, 128
@@ -55,6 +55,9 @@ def bert4rec_dense_names(hid: int, dr: bool = False, comp: str = "", comp_bs: in
     return out
 
 
+# the q / k / v backward of block 0: no feed-forward chain below it (the fp32 and the tile-image forms' names)
+NO_FUSED_FFN = absent(("step_state",) + tuple("f" + n for n in ("pre", "x1", "la", "w2T", "w1T", "woT", "w2T_img", "w1T_img", "woT_img", "dz", "dpre",
+                                                                 "dx1", "dt", "d_o", "ln_part")), flayer=0, train=0, p_drop=0.0)
 N_ENT = 12      # weight-gradient tiles of 128 x 128 per block: q, k, v, o, 4 x w_1, 4 x w_2
 
 
@@ -314,8 +317,8 @@ class Bert4recEngine(SasrecEngine):
             return super()._enqueue_k1(pl, pos0, pos1, tmq, tr, p_drop, lf)
         shp = pl.shape
         src, ld, trn, n, buf = self._tile_images()
-        lib().call("amid_embed_fwd_tiles_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), None, None, shp.B, shp.Tenc, self.D, shp.B * shp.NI,
-                   pl.xg.data_ptr(), None, self.step_state.data_ptr(), 0, 0.0, lf, src, ld, trn, n, 3, buf.data_ptr(), self.s)
+        lib().call_named("amid_embed_fwd_tiles_f32", self._k1_head(pl, None, None, None, 0, 0.0, shp.B * shp.NI), table=self.table.data_ptr(), live=lf,
+                         w_src=src, w_ld=ld, w_tr=trn, n_w=n, w_planes=3, w16_dst=buf.data_ptr())
         pl.tiles_written = True
         if getattr(self, "_sort_owed", False):      # (engine.py _enqueue_k1: a deferred side-stream sort starts behind K1)
             self.enqueue_sort(pl)
@@ -325,14 +328,15 @@ class Bert4recEngine(SasrecEngine):
         lib().call("amid_bert_weight_images_f32", src, ld, trn, n, buf.data_ptr(), self.s)
 
     def _block_img_ptrs(self, l: int):
+        """Block l's weights and their transposes as tile images, under the *_p3_f32 entry points' names."""
         key = ("bert_blk_img", l)
         c = self._ptr_cache.get(key)
         if c is None:
             I = self._img
-            c = dict(w3=ptr_array([I(l, g, j) for j in range(3) for g in (0, 1)]), wo=ptr_array([I(l, g, 3) for g in (0, 1)]),
-                     w1=ptr_array([I(l, g, 4) for g in (0, 1)]), w2=ptr_array([I(l, g, 8) for g in (0, 1)]),
-                     wT3=ptr_array([I(l, g, 12 + j) for j in range(3) for g in (0, 1)]), woT=ptr_array([I(l, g, 15) for g in (0, 1)]),
-                     w1T=ptr_array([I(l, g, 16) for g in (0, 1)]), w2T=ptr_array([I(l, g, 20) for g in (0, 1)]))
+            c = dict(w3_img=ptr_array([I(l, g, j) for j in range(3) for g in (0, 1)]), wo_img=ptr_array([I(l, g, 3) for g in (0, 1)]),
+                     w1_img=ptr_array([I(l, g, 4) for g in (0, 1)]), w2_img=ptr_array([I(l, g, 8) for g in (0, 1)]),
+                     wT3_img=ptr_array([I(l, g, 12 + j) for j in range(3) for g in (0, 1)]), woT_img=ptr_array([I(l, g, 15) for g in (0, 1)]),
+                     w1T_img=ptr_array([I(l, g, 16) for g in (0, 1)]), w2T_img=ptr_array([I(l, g, 20) for g in (0, 1)]))
             self._ptr_cache[key] = c
         return c
 
@@ -344,7 +348,7 @@ class Bert4recEngine(SasrecEngine):
         L, s, shp, D = lib(), self.s, pl.shape, self.D
         B, T = shp.B, shp.Tenc
         live_attn = lf is not None
-        p0, p1 = self._block_ptrs(0), self._block_ptrs(1)
+        p = (self._block_ptrs(0), self._block_ptrs(1))
         # the step's prologue rides in this launch: the key mask (not with a comp module: its tiled mask has a launch of its own) and,
         # when a backward will follow, the transposed weights
         p3 = self._p3(pl)
@@ -353,29 +357,29 @@ class Bert4recEngine(SasrecEngine):
             if build_images and not getattr(pl, "tiles_written", False):      # (the gather K1 of this forward wrote them with extra workgroups)
                 self._enqueue_tile_images()
             pl.tiles_written = False
-            i0, i1 = self._block_img_ptrs(0), self._block_img_ptrs(1)
         sfx = "_p3_f32" if p3 else "_f32"
+        wts = lambda l: (p[l], self._block_img_ptrs(l)) if p3 else (p[l],)      # noqa: E731  (the images' names end in _img: the biases stay p's)
         trl = self._transpose_lists() if pl.need_grad and not p3 else None
         pl.transposed_in_forward = trl is not None or p3
         tr_src, tr_dst, tr_rows, tr_cols = trl or (None,) * 4
         n_tr = len(tr_rows) if trl else 0
         sv = (lambda t: t.data_ptr()) if save else (lambda t: None)
-        L.call("amid_bert_strip_qkv_fwd_pro" + sfx, pl.x[0].data_ptr(), p0["la1"], p0["lb1"], i0["w3"] if p3 else p0["w3"], p0["b3"], B, T, lf, sv(pl.y[0]),
-               pl.q[0].data_ptr(), pl.k[0].data_ptr(), pl.v[0].data_ptr(), None if self.comp else pl.in_seq_d2.data_ptr(), B * T,
-               pl.key_keep.data_ptr(), tr_src, tr_dst, tr_rows, tr_cols, n_tr, s)
-        for l, p in ((0, p0), (1, p1)):
+        dims = dict(B=B, T=T, live=lf, stream=s)
+        # a block's LayerNorm + q / k / v: block 0's is a launch, block 1's the tail of block 0's out-projection / feed-forward launch
+        qkv = lambda l: dict(la=p[l]["la1"], lb=p[l]["lb1"], y=sv(pl.y[l]), q=pl.q[l].data_ptr(), k=pl.k[l].data_ptr(), v=pl.v[l].data_ptr())      # noqa: E731
+        L.call_named("amid_bert_strip_qkv_fwd_pro" + sfx, *wts(0), qkv(0), dims, x=pl.x[0].data_ptr(), seq_d2=None if self.comp else pl.in_seq_d2.data_ptr(),
+                     n_keys=B * T, key_keep=pl.key_keep.data_ptr(), tr_src=tr_src, tr_dst=tr_dst, tr_rows=tr_rows, tr_cols=tr_cols, n_tr=n_tr)
+        att = dict(B=B, T=T, D=D, H=self.H, step_state=st, train=tr, p_drop=BERT_P_DROP, key_keep=pl.key_keep.data_ptr(), stream=s)
+        nxt = prefixed("n", dict(*wts(1)[1:], w3=p[1]["w3"], b3=p[1]["b3"], **qkv(1)))
+        for l in (0, 1):
+            io = dict(q=pl.q[l].data_ptr(), k=pl.k[l].data_ptr(), v=pl.v[l].data_ptr(), o=pl.o[l].data_ptr(), layer=l)
             if live_attn:
-                L.call("amid_attn_bert_fwd_live_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.key_keep.data_ptr(), B, T, D,
-                       self.H, l, st, tr, BERT_P_DROP, pl.o[l].data_ptr(), sv(pl.stats[l]), lf, s)
+                L.call_named("amid_attn_bert_fwd_live_f32", io, att, stats=sv(pl.stats[l]), live=lf)
             else:
-                L.call("amid_attn_fwd_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.key_keep.data_ptr(), B, T, D, self.H,
-                       0, l, st, tr, BERT_P_DROP, pl.o[l].data_ptr(), pl.stats[l].data_ptr(), s)
-            nxt = ((p1["la1"], p1["lb1"], i1["w3"] if p3 else p1["w3"], p1["b3"], sv(pl.y[1]), pl.q[1].data_ptr(), pl.k[1].data_ptr(), pl.v[1].data_ptr())
-                   if l == 0 else (None,) * 8)
-            w = (i0, i1)[l] if p3 else p
-            L.call("amid_bert_strip_oproj_ffn_fwd" + sfx, pl.o[l].data_ptr(), pl.x[l].data_ptr(), w["wo"], p["bo"], p["la2"], p["lb2"], w["w1"],
-                   p["b1"], w["w2"], p["b2"], B, T, lf, l, st, tr, BERT_P_DROP, sv(pl.x1[l]), sv(pl.y2[l]), sv(pl.pre[l]),
-                   sv(pl.h[l]), pl.x[l + 1].data_ptr(), *nxt, s)
+                L.call_named("amid_attn_fwd_f32", io, att, causal=0, stats=pl.stats[l].data_ptr())
+            L.call_named("amid_bert_strip_oproj_ffn_fwd" + sfx, *wts(l), nxt if l == 0 else absent(nxt), dims, o=pl.o[l].data_ptr(), x=pl.x[l].data_ptr(),
+                         la=p[l]["la2"], lb=p[l]["lb2"], layer=l, step_state=st, train=tr, p_drop=BERT_P_DROP, x1=sv(pl.x1[l]), y2=sv(pl.y2[l]),
+                         pre=sv(pl.pre[l]), h=sv(pl.h[l]), x2=pl.x[l + 1].data_ptr())
 
     # ------------------------------------------------------------------ evaluation: test(), train_sr.py:31-128 (engine.enqueue_eval)
     # The batch is amid_pack_indices_live (index marshal + live list), the encoders over the B own-domain sequences, amid_eval_head_f32 with null
@@ -444,29 +448,22 @@ class Bert4recEngine(SasrecEngine):
         if self.comp:
             self._enqueue_comp_front(pl, gather_items=False)
         else:
-            L.call("amid_embed_fwd_live_f32", self.table.data_ptr(), pl.idx_all.data_ptr(), None, None, B, T, D, 0, pl.xg.data_ptr(), None, st, 0,
-                   0.0, lf, s)
+            L.call_named("amid_embed_fwd_live_f32", self._k1_head(pl, None, None, None, 0, 0.0, 0), table=self.table.data_ptr(), live=lf)
         self._enqueue_blocks_strip(pl, lf, st, 0, save=False, build_images=False)
 
     def _enqueue_blocks_rowtile(self, pl: BertPlan, st, tr) -> None:
         L, s, shp, D = lib(), self.s, pl.shape, self.D
         B, T, M = shp.B, shp.Tenc, shp.M
-        fp = self.dense
+        drop = dict(step_state=st, train=tr, p_drop=BERT_P_DROP)
         for l in (0, 1):
-            pre = f"transform{{d}}.{l}"
-            w3 = ptr_array([fp.ptr(f"transform{d}.{l}.attention.linear_layers.{j}.weight") for j in range(3) for d in (1, 2)])
-            b3 = ptr_array([fp.ptr(f"transform{d}.{l}.attention.linear_layers.{j}.bias") for j in range(3) for d in (1, 2)])
-            L.call("amid_bert_qkv_fwd_f32" + pl.rt_suffix, pl.x[l].data_ptr(), self._pp(pre + ".input_sublayer.norm.a_2"), self._pp(pre + ".input_sublayer.norm.b_2"),
-                   w3, b3, M, pl.rpt, pl.y[l].data_ptr(), pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), s)
-            L.call("amid_attn_fwd_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.key_keep.data_ptr(), B, T, D, self.H, 0, l,
-                   st, tr, BERT_P_DROP, pl.o[l].data_ptr(), pl.stats[l].data_ptr(), s)
-            L.call("amid_bert_oproj_fwd_f32" + pl.rt_suffix, pl.o[l].data_ptr(), pl.x[l].data_ptr(), self._pp(pre + ".attention.output_linear.weight"),
-                   self._pp(pre + ".attention.output_linear.bias"), M, pl.rpt, l, st, tr, BERT_P_DROP, pl.x1[l].data_ptr(), s)
-            L.call("amid_bert_ffn1_fwd_f32" + pl.rt_suffix, pl.x1[l].data_ptr(), self._pp(pre + ".output_sublayer.norm.a_2"), self._pp(pre + ".output_sublayer.norm.b_2"),
-                   self._pp(pre + ".feed_forward.w_1.weight"), self._pp(pre + ".feed_forward.w_1.bias"), M, pl.rpt, l, st, tr, BERT_P_DROP,
-                   pl.y2[l].data_ptr(), pl.pre[l].data_ptr(), pl.h[l].data_ptr(), s)
-            L.call("amid_bert_ffn2_fwd_f32" + pl.rt_suffix, pl.h[l].data_ptr(), pl.x1[l].data_ptr(), self._pp(pre + ".feed_forward.w_2.weight"),
-                   self._pp(pre + ".feed_forward.w_2.bias"), M, pl.rpt, l, st, tr, BERT_P_DROP, pl.x[l + 1].data_ptr(), s)
+            p = self._block_ptrs(l)
+            tile = dict(M=M, rows_per_tile=pl.rpt, layer=l, stream=s)
+            io = {n: getattr(pl, n)[l].data_ptr() for n in ("x", "y", "q", "k", "v", "o", "stats", "x1", "y2", "pre", "h")}      # the block's tensors
+            L.call_named("amid_bert_qkv_fwd_f32" + pl.rt_suffix, io, tile, ln_a=p["la1"], ln_b=p["lb1"], w3x2=p["w3"], b3x2=p["b3"])
+            L.call_named("amid_attn_fwd_f32", io, drop, key_keep=pl.key_keep.data_ptr(), B=B, T=T, D=D, H=self.H, causal=0, layer=l, stream=s)
+            L.call_named("amid_bert_oproj_fwd_f32" + pl.rt_suffix, io, tile, drop, w=p["wo"], b=p["bo"])
+            L.call_named("amid_bert_ffn1_fwd_f32" + pl.rt_suffix, io, p, tile, drop, ln_a=p["la2"], ln_b=p["lb2"])
+            L.call_named("amid_bert_ffn2_fwd_f32" + pl.rt_suffix, io, p, tile, drop, x2=pl.x[l + 1].data_ptr())
 
     def enqueue_backward(self, pl: BertPlan, train: bool) -> None:
         L, s, shp, D, F = lib(), self.s, pl.shape, self.D, BERT_FF
@@ -488,11 +485,11 @@ class Bert4recEngine(SasrecEngine):
             self._enqueue_head_dr_bwd(pl, items, ditems)
         elif getattr(self, "_fuse_head", False):
             own = getattr(self, "_live_fwd", False) and self._live_list(pl) is not None      # only the own-domain sequences were encoded
-            L.call("amid_head_fwd_bwd_own_f32" if own else "amid_head_fwd_bwd_f32", pl.x[2].data_ptr(), None, None, items, fp.ptr("predictModule.fc.0.weight"),
-                   fp.ptr("predictModule.fc.0.bias"), fp.ptr("predictModule.fc.2.weight"), fp.ptr("predictModule.fc.2.bias"),
-                   pl.labels.data_ptr(), pl.domain.data_ptr(), B, T, NI, D, self.hid, 0.0, pl.u.data_ptr(), pl.p1.data_ptr(), pl.p2.data_ptr(),
-                   pl.dp1.data_ptr(), pl.dp2.data_ptr(), pl.loss_part.data_ptr(), pl.dxbuf.data_ptr(), ditems, None, pl.sc_part.data_ptr(),
-                   None, None, 0, s)
+            L.call_named("amid_head_fwd_bwd_own_f32" if own else "amid_head_fwd_bwd_f32", self._scorer(), x=pl.x[2].data_ptr(), ln_w=None, ln_b=None,
+                         items=items, labels=pl.labels.data_ptr(), domain_id=pl.domain.data_ptr(), B=B, T=T, NI=NI, D=D, hid=self.hid, eps=0.0,
+                         u=pl.u.data_ptr(), p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(), dp1=pl.dp1.data_ptr(), dp2=pl.dp2.data_ptr(),
+                         loss_part=pl.loss_part.data_ptr(), dx=pl.dxbuf.data_ptr(), ditems=ditems, ln_part=None, sc_part=pl.sc_part.data_ptr(),
+                         tr_src=None, tr_dst=None, n_tr=0, stream=s)
         else:
             L.call_named("amid_head_bwd_f32", self._scorer(), x=pl.x[2].data_ptr(), ln_w=None, u=pl.u.data_ptr(), items=items, p1=pl.p1.data_ptr(),
                          p2=pl.p2.data_ptr(), dp1=pl.dp1.data_ptr(), dp2=pl.dp2.data_ptr(), B=B, T=T, NI=NI, D=D, hid=self.hid, eps=0.0,
@@ -503,15 +500,15 @@ class Bert4recEngine(SasrecEngine):
         lv = None if self.comp else self._live_list(pl)
         live_attn = lv is not None and bool(L.value("amid_attn_bert_live_supported", T, D, self.H))
 
+        att = dict(d_o=pl.d_o.data_ptr(), key_keep=pl.key_keep.data_ptr(), B=B, T=T, D=D, H=self.H, step_state=st, train=tr, p_drop=BERT_P_DROP,
+                   dq=pl.dq.data_ptr(), dk=pl.dk.data_ptr(), dv=pl.dv.data_ptr(), stream=s)
+
         def attn_bwd(l):
+            io = dict(q=pl.q[l].data_ptr(), k=pl.k[l].data_ptr(), v=pl.v[l].data_ptr(), o=pl.o[l].data_ptr(), stats=pl.stats[l].data_ptr(), layer=l)
             if live_attn:
-                L.call("amid_attn_bert_bwd_live_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.o[l].data_ptr(),
-                       pl.stats[l].data_ptr(), pl.d_o.data_ptr(), pl.key_keep.data_ptr(), B, T, D, self.H, l, st, tr, BERT_P_DROP,
-                       pl.dq.data_ptr(), pl.dk.data_ptr(), pl.dv.data_ptr(), lv, s)
+                L.call_named("amid_attn_bert_bwd_live_f32", io, att, live=lv)
             else:
-                L.call("amid_attn_bwd_rows_f32", pl.q[l].data_ptr(), pl.k[l].data_ptr(), pl.v[l].data_ptr(), pl.o[l].data_ptr(), pl.stats[l].data_ptr(),
-                       pl.d_o.data_ptr(), pl.key_keep.data_ptr(), B, T, D, self.H, 0, l, st, tr, BERT_P_DROP, pl.dq.data_ptr(), pl.dk.data_ptr(),
-                       pl.dv.data_ptr(), self._own_rows(pl), s)
+                L.call_named("amid_attn_bwd_rows_f32", io, att, causal=0, row_domain=self._own_rows(pl))
 
         def wgrad(l):
             # weight-gradient tiles need dx-independent operands only: launched before the q / k / v backward overwrites its buffers
@@ -534,50 +531,48 @@ class Bert4recEngine(SasrecEngine):
             p3 = bool(getattr(pl, "p3_fwd", False) and self._p3(pl))     # (this step's forward wrote the tile images, transposes included)
             sfx = "_p3_f32" if p3 else "_f32"
 
-            def ffn_args(l):
-                if p3:
-                    im = self._block_img_ptrs(l)
-                    return (pl.pre[l].data_ptr(), pl.x1[l].data_ptr(), self._pp(f"transform{{d}}.{l}.output_sublayer.norm.a_2"),
-                            im["w2T"], im["w1T"], im["woT"])
-                return (pl.pre[l].data_ptr(), pl.x1[l].data_ptr(), self._pp(f"transform{{d}}.{l}.output_sublayer.norm.a_2"),
-                        ptr_array([self.w2T[l, g].data_ptr() for g in (0, 1)]), ptr_array([self.w1T[l, g].data_ptr() for g in (0, 1)]),
-                        ptr_array([self.wT_sq[l, g, 3].data_ptr() for g in (0, 1)]))
-            ffn_out = (pl.dz.data_ptr(), pl.dpre.data_ptr(), pl.dx1.data_ptr(), pl.dt.data_ptr(), pl.d_o.data_ptr())
-            pre1, x11, la21, w2T1, w1T1, woT1 = ffn_args(1)
-            L.call("amid_bert_strip_ffn_bwd" + sfx, pl.dxbuf.data_ptr(), pre1, x11, la21, w2T1, w1T1, woT1, B, T, lv, 1, st, tr, BERT_P_DROP, *ffn_out,
-                   pl.ln2_part[1].data_ptr(), s)
+            def ffn_block(l):
+                """Block l's feed-forward / out-projection chain under its own launch's names: what it reads, the transposes (tile images
+                or fp32), what it writes (the gradient buffers are shared by the blocks)."""
+                wT = self._block_img_ptrs(l) if p3 else dict(w2T=ptr_array([self.w2T[l, g].data_ptr() for g in (0, 1)]),
+                                                             w1T=ptr_array([self.w1T[l, g].data_ptr() for g in (0, 1)]),
+                                                             woT=ptr_array([self.wT_sq[l, g, 3].data_ptr() for g in (0, 1)]))
+                return dict(wT, pre=pl.pre[l].data_ptr(), x1=pl.x1[l].data_ptr(), la=self._pp(f"transform{{d}}.{l}.output_sublayer.norm.a_2"), layer=l,
+                            dz=pl.dz.data_ptr(), dpre=pl.dpre.data_ptr(), dx1=pl.dx1.data_ptr(), dt=pl.dt.data_ptr(), d_o=pl.d_o.data_ptr(),
+                            ln_part=pl.ln2_part[l].data_ptr())
+            strip = dict(B=B, T=T, live=lv, stream=s)
+            drop = dict(step_state=st, train=tr, p_drop=BERT_P_DROP)
+            L.call_named("amid_bert_strip_ffn_bwd" + sfx, ffn_block(1), strip, drop, dx2=pl.dxbuf.data_ptr())
             for l in (1, 0):
                 attn_bwd(l)
                 wgrad(l)
-                wT3 = (self._block_img_ptrs(l)["wT3"] if p3 else
-                       ptr_array([self.wT_sq[l, g, j].data_ptr() for j in range(3) for g in (0, 1)]))
-                la1 = self._pp(f"transform{{d}}.{l}.input_sublayer.norm.a_2")
+                wT3 = (dict(wT3_img=self._block_img_ptrs(l)["wT3_img"]) if p3 else
+                       dict(wT3=ptr_array([self.wT_sq[l, g, j].data_ptr() for j in range(3) for g in (0, 1)])))
+                qkv = dict(wT3, dq=pl.dq.data_ptr(), dk=pl.dk.data_ptr(), dv=pl.dv.data_ptr(), dx1=pl.dx1.data_ptr(), x=pl.x[l].data_ptr(),
+                           la=self._pp(f"transform{{d}}.{l}.input_sublayer.norm.a_2"), ln_part=pl.ln1_part[l].data_ptr())
                 if l == 1:
-                    L.call("amid_bert_strip_qkv_bwd" + sfx, pl.dq.data_ptr(), pl.dk.data_ptr(), pl.dv.data_ptr(), pl.dx1.data_ptr(), pl.x[1].data_ptr(),
-                           la1, wT3, B, T, lv, None, 0, pl.ln1_part[1].data_ptr(), *ffn_args(0), 0, st, tr, BERT_P_DROP, *ffn_out,
-                           pl.ln2_part[0].data_ptr(), s)
+                    L.call_named("amid_bert_strip_qkv_bwd" + sfx, qkv, prefixed("f", ffn_block(0)), strip, drop, dx=None, zero_dead=0)
                 else:
                     dx_out = pl.dx0 if self.comp else pl.dxg
-                    L.call("amid_bert_strip_qkv_bwd" + sfx, pl.dq.data_ptr(), pl.dk.data_ptr(), pl.dv.data_ptr(), pl.dx1.data_ptr(), pl.x[0].data_ptr(),
-                           la1, wT3, B, T, lv, dx_out.data_ptr(), 1 if lv is not None else 0, pl.ln1_part[0].data_ptr(), None, None, None, None,
-                           None, None, 0, None, 0, 0.0, None, None, None, None, None, None, s)
+                    L.call_named("amid_bert_strip_qkv_bwd" + sfx, qkv, NO_FUSED_FFN, strip, dx=dx_out.data_ptr(), zero_dead=1 if lv is not None else 0)
             pl.p3_fwd = False
         for l in ((1, 0) if not pl.strip else ()):
             pre = f"transform{{d}}.{l}"
             wsq = lambda j: ptr_array([self.wT_sq[l, g, j].data_ptr() for g in (0, 1)])      # noqa: E731
-            L.call("amid_bert_ffn2_bwd_f32" + pl.rt_suffix_b, pl.dxbuf.data_ptr(), pl.pre[l].data_ptr(),
-                   ptr_array([self.w2T[l, g].data_ptr() for g in (0, 1)]), M, pl.rpt_b, l, st, tr, BERT_P_DROP, pl.dz.data_ptr(), pl.dpre.data_ptr(),
-                   s)
-            L.call("amid_bert_ffn1_bwd_f32" + pl.rt_suffix_b, pl.dpre.data_ptr(), pl.dxbuf.data_ptr(), pl.x1[l].data_ptr(),
-                   self._pp(pre + ".output_sublayer.norm.a_2"), ptr_array([self.w1T[l, g].data_ptr() for g in (0, 1)]), wsq(3), M, pl.rpt_b, l, st, tr,
-                   BERT_P_DROP, pl.dx1.data_ptr(), pl.dt.data_ptr(), pl.d_o.data_ptr(), pl.ln2_part[l].data_ptr(), s)
+            tile = dict(M=M, rows_per_tile=pl.rpt_b, layer=l, step_state=st, train=tr, p_drop=BERT_P_DROP, stream=s)
+            # the block's saved tensors and the gradient buffers the blocks share
+            io = dict(pre=pl.pre[l].data_ptr(), x1=pl.x1[l].data_ptr(), x=pl.x[l].data_ptr(), dx2=pl.dxbuf.data_ptr(), dz=pl.dz.data_ptr(),
+                      dpre=pl.dpre.data_ptr(), dx1=pl.dx1.data_ptr(), dt=pl.dt.data_ptr(), d_o=pl.d_o.data_ptr(), dq=pl.dq.data_ptr(),
+                      dk=pl.dk.data_ptr(), dv=pl.dv.data_ptr())
+            L.call_named("amid_bert_ffn2_bwd_f32" + pl.rt_suffix_b, io, tile, w2T=ptr_array([self.w2T[l, g].data_ptr() for g in (0, 1)]))
+            L.call_named("amid_bert_ffn1_bwd_f32" + pl.rt_suffix_b, io, tile, ln_a=self._pp(pre + ".output_sublayer.norm.a_2"),
+                         w1T=ptr_array([self.w1T[l, g].data_ptr() for g in (0, 1)]), woT=wsq(3), ln_part=pl.ln2_part[l].data_ptr())
             attn_bwd(l)
             dx_out = (pl.dx0 if self.comp else pl.dxg) if l == 0 else pl.dxbuf
             wT3 = ptr_array([self.wT_sq[l, g, j].data_ptr() for j in range(3) for g in (0, 1)])
             wgrad(l)
-            L.call("amid_bert_qkv_bwd_f32" + pl.rt_suffix_b, pl.dq.data_ptr(), pl.dk.data_ptr(), pl.dv.data_ptr(), pl.dx1.data_ptr(),
-                   pl.x[l].data_ptr(), self._pp(pre + ".input_sublayer.norm.a_2"), wT3, M, pl.rpt_b, dx_out.data_ptr(), pl.ln1_part[l].data_ptr(),
-                   s)
+            L.call_named("amid_bert_qkv_bwd_f32" + pl.rt_suffix_b, io, tile, ln_a=self._pp(pre + ".input_sublayer.norm.a_2"), wT3x2=wT3,
+                         dx=dx_out.data_ptr(), ln_part=pl.ln1_part[l].data_ptr())
         if self.comp:      # the comp modules' parameter gradients; the rows' own halves + their share of the token group -> dxg
             c, G = self.comp, self.dense.grad
             head = (pl.xg.data_ptr(), pl.dx0.data_ptr(), pl.inc_gate.data_ptr(), pl.inc_S.data_ptr(), pl.inc_sw.data_ptr(),

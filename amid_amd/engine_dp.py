@@ -25,10 +25,10 @@ class DataParallelMixin:
         self._ensure_opt_state()
         fp, D = self.dense, self.D
         id_rows, rows = packed_rows(umax, D)
-        lib().call("amid_optimizer_step_gathered_f32", fp.data.data_ptr(), fp.m.data_ptr(), fp.v.data_ptr(), fp.grad.data_ptr(), fp.numel,
-                   self.table.data_ptr(), self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(), recv.data_ptr(),
-                   world, umax, be.chunk_rows(umax, fp.grad if dense_in_chunk else None) * D, id_rows, rows * D if dense_in_chunk else -1, D,
-                   self.n_rows, self.grad_scale, self.step_state.data_ptr(), self.s)
+        lib().call_named("amid_optimizer_step_gathered_f32", self._adam_dense(), self._adam_rows(), gathered=recv.data_ptr(), world=world, umax=umax,
+                         chunk_floats=be.chunk_rows(umax, fp.grad if dense_in_chunk else None) * D, id_rows=id_rows,
+                         dense_off=rows * D if dense_in_chunk else -1, D=D, sentinel=self.n_rows, grad_scale=self.grad_scale,
+                         step_state=self.step_state.data_ptr(), stream=self.s)
 
     # How the 1.7 MB flat dense gradient crosses the ranks in the graph-pair step: "gather" = behind the sparse rows inside the step's ONE
     # all-gather (every rank sums the world's copies in rank order: one collective's latency, world x 1.7 MB received per rank);

@@ -54,9 +54,9 @@ int amid_step_begin(void* step_state, void* stream);                       /* st
 int amid_gather_rows_f32(const float* table, long long n_rows, int D, const void* idx, int idx_is_i64, long long n_idx,
                          float* out, int* err_flag, void* stream);
 /* concatenate + narrow the four index tensors of a batch: idx_all = [seq_d1 | seq_d2 | (i_node, neg)[b]] */
-/* step_state_to_bump (optional): the same launch performs amid_step_begin (one launch fewer per step) */
+/* step_state (optional): the same launch performs amid_step_begin (one launch fewer per step) */
 int amid_pack_indices(const long long* i_node, const long long* neg, const long long* seq_d1, const long long* seq_d2,
-                      int B, int T, int n_neg, long long n_rows, int* idx_all, int* err_flag, void* step_state_to_bump, void* stream);
+                      int B, int T, int n_neg, long long n_rows, int* idx_all, int* err_flag, void* step_state, void* stream);
 /* the same with the epoch's batches resident in HBM (train_sr.py:185-199: the reference moves each batch with .cuda() inside the
  * loop): `pool` holds n_pool packed batch images of `pool_stride` int64 words ([i_node B][neg B n_neg][seq_d1 B T][seq_d2 B T]
  * [tail words]); the launch consumes image (step + phase) mod n_pool by the DEVICE step counter, mirrors its in_words words into
@@ -165,21 +165,21 @@ int amid_grad_tail_pack_f32(const float* grad_rows, const int* pos_sorted, const
 /* ---- K4 optimizer ----------------------------------------------------------------------------
  * replaces: torch.optim.Adam(model.parameters(), lr).step(), train_sr.py:480, :215 (dense over the table).
  * lazy rows: m, v [n_rows, D], last [n_rows] int32 (0 = never touched). */
-int amid_lazy_adam_catchup_f32(float* table, float* m, float* v, int* last, const int* uniq_ids, const int* n_uniq, int n_uniq_max,
+int amid_lazy_adam_catchup_f32(float* table, float* m_tab, float* v_tab, int* last, const int* uniq_ids, const int* n_uniq, int n_uniq_max,
                                int D, const void* step_state, void* stream);
 /* catch-up driven by the raw (non-unique) index list: needs no sort, so the sort can overlap the forward pass */
-int amid_lazy_adam_catchup_positions_f32(float* table, float* m, float* v, int* last, const int* idx, int n_idx, int D,
+int amid_lazy_adam_catchup_positions_f32(float* table, float* m_tab, float* v_tab, int* last, const int* idx, int n_idx, int D,
                                          const void* step_state, void* stream);
 /* ... carrying phase 1 of a sort plan (amid_sort_plan_pack) as extra workgroups in front of its own -- or, sort_phase = 6, ALL FIVE phases
  * chained in this one launch (the riders meet at a barrier of their own between the phases): for steps without five launches to ride in, whose
  * sort ran as a dozen small launches on a side stream.  The chain takes plans with keys below 2^20 over at most
  * amid_sort_chain_max_indices() indices; AMID_ERR_UNSUPPORTED otherwise. */
 int amid_sort_chain_max_indices(void);
-int amid_lazy_adam_catchup_positions_sort_f32(float* table, float* m, float* v, int* last, const int* idx, int n_idx, int D,
+int amid_lazy_adam_catchup_positions_sort_f32(float* table, float* m_tab, float* v_tab, int* last, const int* idx, int n_idx, int D,
                                               const void* step_state, const void* sort_plan, int sort_phase, void* stream);
-int amid_lazy_adam_apply_f32(float* table, float* m, float* v, int* last, const int* uniq_ids, const int* n_uniq, int n_uniq_max,
+int amid_lazy_adam_apply_f32(float* table, float* m_tab, float* v_tab, int* last, const int* uniq_ids, const int* n_uniq, int n_uniq_max,
                              const float* uniq_grad, float grad_scale, int D, const void* step_state, void* stream);
-int amid_lazy_adam_flush_f32(float* table, float* m, float* v, int* last, long long n_rows, int D, const void* step_state, void* stream);
+int amid_lazy_adam_flush_f32(float* table, float* m_tab, float* v_tab, int* last, long long n_rows, int D, const void* step_state, void* stream);
 int amid_adam_dense_f32(float* p, float* m, float* v, const float* g, long long n, float grad_scale, const void* step_state, void* stream);
 /* amid_adam_dense_f32 + amid_lazy_adam_apply_f32 as ONE launch */
 int amid_optimizer_step_f32(float* p, float* m, float* v, const float* g, long long n, float* table, float* m_tab, float* v_tab,
@@ -720,40 +720,42 @@ int amid_live_list_i32(const long long* domain, int B, int* live, void* stream);
 /* amid_pack_indices / amid_pack_indices_pool with the live list written by the same launch (the pool images carry the batch's
  * domain ids in the B words behind the index words: SasrecEngine.pack_batch) */
 int amid_pack_indices_live(const long long* i_node, const long long* neg, const long long* seq_d1, const long long* seq_d2, int B, int T,
-                           int n_neg, long long n_rows, int* idx_all, int* err_flag, void* step_state_to_bump, const long long* domain,
+                           int n_neg, long long n_rows, int* idx_all, int* err_flag, void* step_state, const long long* domain,
                            int* live, void* stream);
 int amid_pack_indices_pool_live(const long long* pool, long long pool_stride, int n_pool, long long phase, long long* in_pack,
                                 int in_words, int B, int T, int n_neg, long long n_rows, int* idx_all, int* err_flag, void* step_state,
                                 int* live, void* stream);
 /* amid_embed_bwd_f32 / amid_embed_bwd_rows_f32 (row_domain optional) carrying phase 5 of a sort plan as extra workgroups */
-int amid_embed_bwd_sort_f32(float* dxg, const unsigned char* tmq, int B, int T, int D, int nsplit, float* dpos_part, const void* rng_state,
+int amid_embed_bwd_sort_f32(float* dxg, const unsigned char* tmq, int B, int T, int D, int nsplit, float* dpos_part, const void* step_state,
                             int train, float p_drop, const long long* row_domain, const void* sort_plan, int sort_phase, void* stream);
 int amid_embed_fwd_live_f32(const float* table, const int* idx_all, const float* pos0, const float* pos1, int B, int T, int D,
-                            int n_item_rows, float* xg, unsigned char* tmq, const void* rng_state, int train, float p_drop,
+                            int n_item_rows, float* xg, unsigned char* tmq, const void* step_state, int train, float p_drop,
                             const int* live, void* stream);
 /* amid_embed_fwd_live_f32 that also writes the step's compact index list over the live sequences + the items (B T + n_item_rows
  * entries): idx_c[i] = the id at walk position i, row_c[i] = that position's row in the full [2 B T + items] layout (where its
  * gradient will stand).  Sort (amid_sort_unique_rows_i32), segment reduce and row Adam of the step then run on half the entries:
  * the dead sequences' gradient rows are exact zeros (train_sr.py:205-211). */
 int amid_embed_fwd_live_compact_f32(const float* table, const int* idx_all, const float* pos0, const float* pos1, int B, int T, int D,
-                                    int n_item_rows, float* xg, unsigned char* tmq, const void* rng_state, int train, float p_drop,
+                                    int n_item_rows, float* xg, unsigned char* tmq, const void* step_state, int train, float p_drop,
                                     const int* live, int* idx_c, int* row_c, void* stream);
 /* K1 with the lazy-Adam catch-up folded in (replaces amid_lazy_adam_catchup_positions_f32 + amid_embed_fwd*_f32 of a train step;
  * reference: the dense torch.optim.Adam of train_sr.py:480 moves every row every step, so a row idle since step `last` owes the
  * zero-gradient steps last + 1 .. t - 1 before model_seq.py:418-421 reads it): the owed steps are replayed IN REGISTERS for the value
  * written to xg; table / m / v / last are only read -- amid_optimizer_step_f32 of the same step replays them again (bit-identically) in
  * front of the real step.  sort_plan != NULL: phase 1 of the step's index sort rides as extra workgroups.  live, idx_c, row_c: NULL or
- * as amid_embed_fwd_live_f32 / amid_embed_fwd_live_compact_f32. */
+ * as amid_embed_fwd_live_f32 / amid_embed_fwd_live_compact_f32.  step_state is what every K1 form calls so: the dropout counters' seed and
+ * step.  adam_state is the state the replay takes its Adam coefficients from -- a parameter of this entry alone, in no shared table, so a
+ * caller always names it; the driver hands the same buffer to both. */
 int amid_embed_fwd_replay_f32(const float* table, const float* m_tab, const float* v_tab, const int* last, const int* idx_all,
                               const float* pos0, const float* pos1, int B, int T, int D, int n_item_rows, float* xg,
-                              unsigned char* tmq, const void* rng_state, int train, float p_drop, const int* live, int* idx_c,
+                              unsigned char* tmq, const void* step_state, int train, float p_drop, const int* live, int* idx_c,
                               int* row_c, const void* adam_state, const void* sort_plan, int sort_phase, void* stream);
 /* K1 (the gather: live / idx_c / row_c as amid_embed_fwd_live(_compact)_f32, NULL = every sequence / no compact list) with this step's bf16
  * fragment images of n_w (<= 24) square [D][D] weights written by extra workgroups of the same launch (what amid_sas_weights_bf16_planes
  * does as a launch of its own): w16_dst [n_w][planes][D][D] bf16, planes = 1 or 3; w16t_dst: NULL, or the same for the weights' TRANSPOSES
  * (the operands of the backward strips, amid_sas_strip_*_bwd_* with mma_bf16 = 3).  D = 128. */
 int amid_embed_fwd_w16_f32(const float* table, const int* idx_all, const float* pos0, const float* pos1, int B, int T, int D, int n_item_rows,
-                           float* xg, unsigned char* tmq, const void* rng_state, int train, float p_drop, const int* live, int* idx_c,
+                           float* xg, unsigned char* tmq, const void* step_state, int train, float p_drop, const int* live, int* idx_c,
                            int* row_c, const float* const* w_src, int n_w, int w_planes, void* w16_dst, void* w16t_dst, void* stream);
 /* 1 when the matrix-core attention kernels cover the shape (causal, T <= 64, H <= 8, head dim 16 or 8): the live-list entries below */
 int amid_attn_live_supported(int T, int D, int H, int causal);
@@ -846,7 +848,7 @@ int amid_sas_strip_qkv_bwd_sort_f32(const float* dq, const float* dk, const floa
                                int flayer, const void* step_state, int train, float p_drop, float* fdpre2, float* fdpre1, float* fdr,
                                float* fd_o, float* fln_part, const void* sort_plan, int sort_phase, int mma_bf16, void* stream);
 
-int amid_embed_bwd_rows_f32(float* dxg, const unsigned char* tmq, int B, int T, int D, int nsplit, float* dpos_part, const void* rng_state,
+int amid_embed_bwd_rows_f32(float* dxg, const unsigned char* tmq, int B, int T, int D, int nsplit, float* dpos_part, const void* step_state,
                             int train, float p_drop, const long long* row_domain, void* stream);   /* amid_embed_bwd_f32 behind the *_rows kernels: the dead sequences' rows are zero-filled, not read */
 
 /* the 64-row (_rt4) build exists for the backward row-tile kernels only (the live-row backward of the headline shape: 50 rows per tile) */
@@ -894,8 +896,8 @@ int amid_bert_qkv_bwd_f32_rt4(const float* dq, const float* dk, const float* dv,
  * launch on the stream must be one of amid_embed_fwd*_f32 (it re-joins the step state's two counters).
  * replaces: amid_pack_indices_pool_live + amid_lazy_adam_catchup_positions_sort_f32. */
 int amid_step_head_f32(const long long* pool, long long pool_stride, int n_pool, long long phase, long long* in_pack, int in_words, int B, int T,
-                       int n_neg, long long n_rows, int* idx_all, int* idx_c, int* row_c, int* live, int* err_flag, float* table, float* m,
-                       float* v, int* last, int D, void* step_state, const void* sort_plan, void* stream);
+                       int n_neg, long long n_rows, int* idx_all, int* idx_c, int* row_c, int* live, int* err_flag, float* table, float* m_tab,
+                       float* v_tab, int* last, int D, void* step_state, const void* sort_plan, void* stream);
 /* amid_sas_strip_qkv_bwd(_sort)_f32 without the fused feed-forward backward, with the embedding layer's element-wise backward applied to dx
  * before it is stored: the input dropout's keep bits (site SITE_EMB, p = emb_p_drop) redrawn from step_state and the "== 0" bits of
  * emb_tmq (model_seq.py:361-366) -- what amid_embed_bwd_f32 does in a pass of its own.  sort_plan NULL or a plan whose phase 4 rides. */
@@ -1081,8 +1083,8 @@ int amid_sas_seq_fwd_gather_infer_f32(int n_layers, float* xout, const float* co
 /* amid_step_head_f32 + the step's weight images by extra workgroups (amid_embed_fwd_w16_f32's riders): w_src = n_w square [D][D] fp32 weights,
  * w16_dst [n_w][w_planes][D][D] bf16, w16t_dst (optional) the images of their transposes.  D = 128, n_w (x 2 with transposes) <= 96. */
 int amid_step_head_w16_f32(const long long* pool, long long pool_stride, int n_pool, long long phase, long long* in_pack, int in_words, int B, int T,
-                           int n_neg, long long n_rows, int* idx_all, int* idx_c, int* row_c, int* live, int* err_flag, float* table, float* m,
-                           float* v, int* last, int D, void* step_state, const void* sort_plan, const float* const* w_src, int n_w, int w_planes,
+                           int n_neg, long long n_rows, int* idx_all, int* idx_c, int* row_c, int* live, int* err_flag, float* table, float* m_tab,
+                           float* v_tab, int* last, int D, void* step_state, const void* sort_plan, const float* const* w_src, int n_w, int w_planes,
                            void* w16_dst, void* w16t_dst, void* stream);
 
 /* amid_grad_tail_live_f32 (hidg = NULL) and amid_optimizer_step_spans_f32 as ONE launch (round 6): every producer of a gradient slice applies
@@ -1155,7 +1157,7 @@ int amid_eval_head_u_f32(const float* u_src, long long u_dom_stride, const float
  * amid_full_rank_f32: rank[b] = #{c in pool - own(b) : p(u_b, c) > p(u_b, pos[b]) - fix_value}, rank_raw[b] the same with 0 (test()'s rule,
  * train_sr.py:114-115); scores [B, n_cols] optional: scores[b][i] = p(u_b, pool_dom(b)[i]) (columns past that pool not written).
  * amid_topk_f32: ids / scores [B, k]: the k best candidates of pool_dom(b) (minus own(b) with exclude_history), best first, ties to the
- * lower id; fewer than k candidates: id -1, score -inf.  1 <= k <= 256.
+ * lower id; fewer than k candidates: id -1, score -inf.  1 <= k <= 256 (the parameter top_k: k names the attention keys elsewhere).
  * Both: D 64 / 128, hid 16 / 32 / 64 (else AMID_ERR_UNSUPPORTED); ids outside [0, n_rows) raise AMID_FLAG_INDEX_RANGE in *flags; workspace:
  * amid_full_rank_workspace_bytes(B, n_pool_d1, n_pool_d2, hid, k) bytes (k = 0: the rank). */
 long long amid_full_rank_workspace_bytes(int B, int n_pool_d1, int n_pool_d2, int hid, int k);
@@ -1167,7 +1169,7 @@ int amid_full_rank_f32(const float* u, long long u_dom_stride, const long long* 
 int amid_topk_f32(const float* u, long long u_dom_stride, const long long* domain_id, int B, const long long* pool_d1, int n_pool_d1,
                   const long long* pool_d2, int n_pool_d2, const long long* own_items, const int* own_off, const int* rows,
                   const float* table, long long n_rows, const float* w1, const float* b1, const float* w2, const float* b2, int D,
-                  int hid, int k, int exclude_history, void* workspace, int* flags, long long* ids, float* scores, void* stream);
+                  int hid, int top_k, int exclude_history, void* workspace, int* flags, long long* ids, float* scores, void* stream);
 /* amid_topk_f32 cut where it stops depending on the user, for the batches of a whole dataset against frozen weights:
  * amid_topk_items_f32: the item halves W1[:, D:] table[c] of every candidate of both pools into the workspace's ci region (fr_items_kernel's
  * launch alone; that region's place depends on B and hid only, so one call serves every k).
@@ -1179,7 +1181,7 @@ int amid_topk_items_f32(int B, const long long* pool_d1, int n_pool_d1, const lo
 int amid_topk_users_f32(const float* u, long long u_dom_stride, const long long* domain_id, int B, const long long* pool_d1, int n_pool_d1,
                         const long long* pool_d2, int n_pool_d2, const long long* own_items, const int* own_off, const int* rows,
                         const float* table, long long n_rows, const float* w1, const float* b1, const float* w2, const float* b2, int D,
-                        int hid, int k, int exclude_history, void* workspace, int* flags, long long* ids, float* scores, void* stream);
+                        int hid, int top_k, int exclude_history, void* workspace, int* flags, long long* ids, float* scores, void* stream);
 /* History sets from the sequences (csrc/own_sets.hip): own(b) = the sorted unique ids (signed order, the pad id kept) of row b's own-domain
  * sequence, domain_id[b] != 0 ? seq_d2[b] : seq_d1[b] (seq_d1, seq_d2 [B, T], domain_id [B]), as the CSR list amid_topk_f32 reads with
  * rows = 0 .. B - 1: own (capacity B * T; words past own_off[B] are not written), own_off [B + 1].  cnt: [B] ints of scratch.  Two launches on
@@ -1344,7 +1346,7 @@ int amid_bert_comp_bwd_shard_f32(const float* xg, const float* dx0, const float*
                                  float* const* db_nn, float* const* dw_bs, float* const* db_bs, float* dxg, void* stream);
 /* K1 (amid_embed_fwd_live_f32 / amid_embed_fwd_f32 by `live`) carrying amid_bert_weight_images_f32's tiles as extra workgroups of the gather */
 int amid_embed_fwd_tiles_f32(const float* table, const int* idx_all, const float* pos0, const float* pos1, int B, int T, int D, int n_item_rows,
-                             float* xg, unsigned char* tmq, const void* rng_state, int train, float p_drop, const int* live,
+                             float* xg, unsigned char* tmq, const void* step_state, int train, float p_drop, const int* live,
                              const float* const* w_src, const int* w_ld, const int* w_tr, int n_w, int w_planes, void* w16_dst, void* stream);
 int amid_bert_strip_qkv_fwd_pro_p3_f32(const float* x, const float* const* la, const float* const* lb, const float* const* w3_img,
                                        const float* const* b3, int B, int T, const int* live, float* y, float* q, float* k, float* v,
@@ -1419,7 +1421,7 @@ int amid_pool_prepare_i32(const long long* pool, long long pool_stride, int n_po
                           int* slab, long long slab_stride, void* workspace, void* stream);
 int amid_step_head_prepared_f32(const long long* pool, long long pool_stride, int n_pool, long long phase, long long* in_pack, int in_words,
                                 int B, int T, int n_neg, long long n_rows, int* idx_all, int* idx_c, int* row_c, int* live, int* err_flag,
-                                float* table, float* m, float* v, int* last, int D, void* step_state, const void* sort_plan, const int* slab,
+                                float* table, float* m_tab, float* v_tab, int* last, int D, void* step_state, const void* sort_plan, const int* slab,
                                 long long slab_stride, const float* const* w_src, int n_w, int w_planes, void* w16_dst, void* w16t_dst,
                                 void* stream);
 int amid_sas_strip_qkv_bwd_scorer_f32(const float* dq, const float* dk, const float* dv, const float* dr, const float* x,
