@@ -657,7 +657,9 @@ __device__ __forceinline__ void transpose_extra(const HeadArgs& a, float* __rest
 // left in LDS (returned pointer; a region of s.ci).
 // FUSED = true: called right after scorer_fwd_part in the same workgroup -- W1^T, the user vectors and their hidden pre-activations
 // (s.w1t, s.u_s, s.au) are still in LDS, and with NI <= 64 so are the item pre-activations (s.ci)
-template <bool FUSED, bool ACC>
+// DZ = true: a.dp1 / a.dp2 hold dLoss/dz, the gradient on the LOGITS (the listwise objectives, head_listwise.hip), and are taken as they
+// are: no p (1 - p) factor, p1 / p2 are not read
+template <bool FUSED, bool ACC, bool DZ = false>
 __device__ __forceinline__ float* scorer_bwd_part(const HeadArgs& a, const HeadLds& s, int b, const Tg tg, float* __restrict__ dit_lds = nullptr) {
     const int D = a.D, hid = a.hid, NI = a.NI;
     const int P = (hid * 2 * D + 2 * hid + 1 + 3) & ~3;      // amid_scorer_part_floats: rows padded to whole float4s
@@ -686,7 +688,8 @@ __device__ __forceinline__ float* scorer_bwd_part(const HeadArgs& a, const HeadL
             for (int n = 0; n < nn; ++n) {
                 const long long o = (long long)b * NI + n0 + n;
                 const float p1 = pd != nullptr ? pd[n] : a.p1[o], p2 = pd != nullptr ? pd[4 + n] : a.p2[o];
-                const float dz1 = (pd != nullptr ? pd[8 + n] : a.dp1[o]) * p1 * (1.f - p1), dz2 = (pd != nullptr ? pd[12 + n] : a.dp2[o]) * p2 * (1.f - p2);
+                float dz1 = (pd != nullptr ? pd[8 + n] : a.dp1[o]) * p1 * (1.f - p1), dz2 = (pd != nullptr ? pd[12 + n] : a.dp2[o]) * p2 * (1.f - p2);
+                if constexpr (DZ) { dz1 = a.dp1[o]; dz2 = a.dp2[o]; }
                 const float c = s.ci[n * (hid + 1) + j];
                 const float h1 = fmaxf(s.au[j] + c, 0.f), h2 = fmaxf(s.au[hid + j] + c, 0.f);
                 const float g1 = h1 > 0.f ? dz1 * w2j : 0.f, g2 = h2 > 0.f ? dz2 * w2j : 0.f;
@@ -702,7 +705,8 @@ __device__ __forceinline__ float* scorer_bwd_part(const HeadArgs& a, const HeadL
                 const long long o = (long long)b * NI + n0 + n;
                 const float* pd = s.st.pd;
                 const float p1 = pd != nullptr ? pd[n] : a.p1[o], p2 = pd != nullptr ? pd[4 + n] : a.p2[o];
-                acc += (pd != nullptr ? pd[8 + n] : a.dp1[o]) * p1 * (1.f - p1) + (pd != nullptr ? pd[12 + n] : a.dp2[o]) * p2 * (1.f - p2);
+                if constexpr (DZ) acc += a.dp1[o] + a.dp2[o];
+                else acc += (pd != nullptr ? pd[8 + n] : a.dp1[o]) * p1 * (1.f - p1) + (pd != nullptr ? pd[12 + n] : a.dp2[o]) * p2 * (1.f - p2);
             }
             s.dw2[hid] += acc;
         }

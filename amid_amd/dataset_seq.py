@@ -158,20 +158,24 @@ class DeviceBatches:
     """DataLoader(batch_size, shuffle, drop_last=True) over a tokenised dataset resident on the device."""
 
     def __init__(self, ds: DualDomainSeqDataset, batch_size: int, shuffle: bool, device, seed: int = 0, rank: int = 0, world: int = 1,
-                 negatives: str = "device", counts=None, power: float = 1.0):
+                 negatives: str = "device", counts=None, power: float = 1.0, train_negs: int = 1):
         """rank / world: data parallel -- every rank walks the same shuffled order (same seed) in global batches of
         world x batch_size rows and keeps its own contiguous slice (DistributedSampler-style, drop_last).
         negatives: "device" = drawn per epoch by amid_sample_negatives_i64; "fixture" = the draw stored with a tokenised fixture
         (DualDomainSeqDataset.from_tokenised: what the reference's random.sample produced under random.seed(0); needs no GPU);
         "popularity" = drawn per epoch by amid_sample_negatives_weighted_i64 with weights popularity_weights(counts, power), counts a
-        pair aligned with ds.pool (None: item_counts(ds)); the weight prefixes are built here, once, and stay on the device."""
+        pair aligned with ds.pool (None: item_counts(ds)); the weight prefixes are built here, once, and stay on the device.
+        train_negs: negatives per row of a TRAINING dataset (1 .. 1023; the reference's loader draws one, dataset_seq.py:198), in every
+        `negatives` mode; an evaluation dataset keeps its neg_nums."""
         self.ds, self.bs, self.shuffle, self.device = ds, batch_size, shuffle, torch.device(device)
         self.rank, self.world = rank, world
         if negatives not in ("device", "fixture", "popularity"):
             raise ValueError(f"negatives must be 'device', 'fixture' or 'popularity', got {negatives!r}")
         if negatives != "popularity" and (counts is not None or power != 1.0):
             raise ValueError("counts / power belong to negatives='popularity'")
-        if negatives == "fixture" and (not hasattr(ds, "ref_neg") or ds.ref_neg.shape[1] < (1 if ds.isTrain else ds.neg_nums)):
+        if not (isinstance(train_negs, int) and 1 <= train_negs <= 1023):
+            raise ValueError(f"train_negs must be an int in 1..1023, got {train_negs!r}")
+        if negatives == "fixture" and (not hasattr(ds, "ref_neg") or ds.ref_neg.shape[1] < (train_negs if ds.isTrain else ds.neg_nums)):
             raise ValueError("negatives='fixture' needs a tokenised dataset carrying enough stored negatives")
         self.negatives = negatives
         to = lambda a: torch.from_numpy(a).to(self.device)       # noqa: E731
@@ -193,7 +197,7 @@ class DeviceBatches:
         self.own_off = torch.from_numpy(off).to(self.device)
         self.own = to(np.concatenate(ds.own_items) if len(ds) else np.zeros(0, np.int64))
         self.seed, self.epoch = int(seed), 0
-        k = 1 if ds.isTrain else ds.neg_nums
+        k = train_negs if ds.isTrain else ds.neg_nums
         self.k = k
         for r, o in enumerate(ds.own_items):
             if k + len(o) > len(ds.pool[int(ds.domain_id[r] != 0)]):

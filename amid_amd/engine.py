@@ -49,6 +49,7 @@ NO_POS_ROWS = absent(("live", "dpos0", "dpos1"), B=0, T=0)          # a gradient
 NO_SCORER_SUMS = absent(("hidg", "u", "items", "dW1", "db1", "dW2", "db2"), NI=0, hid=0)
 NO_FUSED_FFN = absent(("tmq", "step_state") + tuple("f" + n for n in ("h", "r", "ln_w", "w1T", "w2T", "woT", "dpre2", "dpre1", "dr", "d_o", "ln_part")),
                       flayer=0, train=0, p_drop=0.0)          # (the q / k / v backward of layer 0: no feed-forward chain below it)
+LOSSES = ("bce", "softmax", "bpr")        # a train step's objective; the index is amid_scorer_listwise_fwd_bwd_f32's `kind` (1, 2)
 NO_NEXT_QKV = absent(prefixed("n", dict.fromkeys(("qn", "q", "k", "v", "ln_w", "ln_b", "w_in", "b_in"))))
 
 
@@ -84,9 +85,21 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
 
     def __init__(self, item_length: int, emb_dim: int, seq_len: int, hid_dim: int, device="cuda:0", lr: float = 5e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0, itc_bs: int = 0, itc_threshold: float = 0.5, dr: bool = False,
-                 dr_e_w: float = 0.1, compute: str = "f32", inc_bs: int = 0, inc_threshold: float = 0.5):
+                 dr_e_w: float = 0.1, compute: str = "f32", inc_bs: int = 0, inc_threshold: float = 0.5, loss: str = "bce"):
         """itc_bs > 0: SASRec(isItC=True, bs=itc_bs, threshold2=itc_threshold) -- InterComp after the encoders
-        (model_seq.py:426-431); every batch must then hold exactly itc_bs rows (trans_bs is Linear(bs, 1) over the batch)."""
+        (model_seq.py:426-431); every batch must then hold exactly itc_bs rows (trans_bs is Linear(bs, 1) over the batch).
+        loss: the objective of a train step over a row's candidates (column 0 the positive): "bce" the reference's masked BCE
+        (train_sr.py:203-212), "softmax" / "bpr" sampled softmax / BPR on the own domain's logits (csrc/head_listwise.hip; DESIGN.md
+        section 17).  Evaluation (test(), eval_ranks, recommend*) does not depend on it."""
+        if loss not in LOSSES:
+            raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+        if loss != "bce":
+            why = ("isDR: the doubly-robust objectives are written on the BCE value" if dr else
+                   "compute = 'bf16': the listwise step is built in fp32" if compute == "bf16" else
+                   "isInC / a comp module in front of the encoders: the listwise step is not built for it" if inc_bs else "")
+            if why:
+                raise ValueError(f"loss = {loss!r} is refused with {why}")
+        self.loss = loss
         L = lib()        # raises AmidLibraryError when the HIP library is missing: no fallback
         if self.SEQ_FWD_VARIANT:          # A/B measurements of the fused forward's builds (amid_sas_seq_fwd_variant)
             L.value("amid_sas_seq_fwd_variant", int(self.SEQ_FWD_VARIANT))
@@ -664,7 +677,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         """The conditions of the folded twelve-launch step that do not depend on how the backward runs (_tail2_ok adds those)."""
         return bool(self.FUSED_TAIL and self._fold_ctx() and self.SORT_RIDERS and pl.need_grad and self.D == 128
                     and self._ceff() == "f32" and not self.dr and not self.itc_bs and not self.inc_bs and not getattr(self, "comp", "")
-                    and pl.shape.NI > 1 and self.FUSED_HEAD and self.BWD_SPLIT and pl.strip
+                    and 1 < pl.shape.NI <= 64 and self.FUSED_HEAD and self.BWD_SPLIT and pl.strip      # (the head's hidden-gradient form: one item chunk)
                     and self.input_pool(pl) is not None and self.live_forward_ok(pl) and self._wgrad_mode(self.D) == 3
                     and not self._fold_catchup(pl) and self._sort_plan_c(pl) is not None and (pl.n_compact + 2047) // 2048 <= 12 * pl.splits)
 
@@ -673,7 +686,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         # (inside enqueue_train_step the segment reduce's runs across chunks are finished by THIS step's optimizer launch; inside
         # enqueue_local_grads -- what a data-parallel exchange ships -- by a launch of their own behind the tail, amid_grad_tail_live_dp_f32)
         return bool(self.FUSED_TAIL and self._fold_ctx() and self.SORT_RIDERS and pl.need_grad and self.D == 128 and self._ceff() == "f32" and not self.dr
-                    and not self.itc_bs and not self.inc_bs and not getattr(self, "comp", "") and pl.shape.NI > 1
+                    and not self.itc_bs and not self.inc_bs and not getattr(self, "comp", "") and 1 < pl.shape.NI <= 64
                     and self.FUSED_HEAD and self.live_forward_ok(pl) and self._p3_bwd_for(pl) and self._wgrad_mode(self.D) == 3
                     and not self._fold_catchup(pl) and self._sort_plan_c(pl) is not None
                     and (pl.n_compact + 2047) // 2048 <= 12 * pl.splits)
@@ -706,6 +719,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
     def live_forward_ok(self, pl: SasrecPlan) -> bool:
         """Whether this engine's train step on `pl` encodes the live sequences only (see _enqueue_fwd_bwd)."""
         return bool(getattr(pl, "strip", False) and not self.itc_bs and not self.dr and not self.inc_bs and self.FUSED_HEAD and self.LIVE_FORWARD
+                    and self.loss == "bce"      # (a listwise step's head reads the user vectors of a launch of its own: every sequence is encoded)
                     and lib().value("amid_attn_live_supported", pl.shape.Tenc, self.D, self.H, 1))
 
     def n_sparse_train(self, pl: SasrecPlan, dp: bool = False) -> int:
@@ -960,6 +974,8 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
         if not gather_items:
             raise ValueError("enqueue_forward: the heads read the candidates' gathered rows (gather_items=False goes with head=False)")
         items = pl.xg.data_ptr() + 4 * 2 * shp.Mi * D
+        if self._listwise_fwd(pl, with_loss, sum_loss):
+            return
         if (self.dr or self.itc_bs) and getattr(self, "_fuse_scorers", False) and with_loss and not sum_loss:
             self._enqueue_user_vectors(pl)           # train step: the scorers run as ONE forward + loss + backward launch in enqueue_backward
             return
@@ -1121,6 +1137,37 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
                          dr_loss_part=pl.dr_loss_part.data_ptr() if self.dr else None, du=pl.du.data_ptr(), ditems=ditems,
                          sc_part=pa(o[4].data_ptr() for o in outs), tr_src=tr_src, tr_dst=tr_dst, n_tr=n_tr, stream=self.s)
 
+    # ---- listwise objectives (loss = "softmax" | "bpr"): user vectors -> amid_scorer_listwise_fwd_bwd_f32 -> their backward ----
+    def _listwise_fwd(self, pl: SasrecPlan, with_loss: bool, sum_loss: bool) -> bool:
+        """The forward's head under a listwise loss: the user vectors only (pl.u; InterComp's mix included).  The scorer's forward, the
+        objective and the scorer's backward are ONE launch, enqueued by the backward that follows (_listwise_bwd): pl.p1 / pl.p2, the loss
+        partials and -- sum_loss -- pl.loss are there after enqueue_backward.  False: not this engine's case (the BCE heads run)."""
+        pl.listwise_owed = False
+        if self.loss == "bce" or not with_loss:
+            return False
+        if getattr(pl, "itc_world", 1) != 1 or getattr(pl, "inc_world", 1) != 1:
+            raise ValueError(f"loss = {self.loss!r}: the listwise step is single-GPU (a data-parallel shard of a comp batch is refused)")
+        if pl.shape.NI < 2 or pl.shape.NI > 1024:
+            raise ValueError(f"loss = {self.loss!r} needs 1 .. 1023 negatives a row, got {pl.shape.NI - 1}")
+        self._enqueue_user_vectors(pl)
+        pl.listwise_owed, pl.listwise_sum = True, bool(sum_loss)
+        return True
+
+    def _listwise_bwd(self, pl: SasrecPlan, items: int, ditems: int, tr_src, tr_dst, n_tr: int) -> bool:
+        """The launch _listwise_fwd left to the backward (pl.dp1 / pl.dp2 then hold dLoss/dz, not dLoss/dp), and the user vectors' backward."""
+        if not getattr(pl, "listwise_owed", False):
+            return False
+        pl.listwise_owed = False
+        shp = pl.shape
+        lib().call_named("amid_scorer_listwise_fwd_bwd_f32", self._scorer(), u=pl.u.data_ptr(), items=items, domain_id=pl.domain.data_ptr(),
+                         kind=LOSSES.index(self.loss), B=shp.B, NI=shp.NI, D=self.D, hid=self.hid, p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(),
+                         dz1=pl.dp1.data_ptr(), dz2=pl.dp2.data_ptr(), loss_part=pl.loss_part.data_ptr(), du=pl.du.data_ptr(), ditems=ditems,
+                         sc_part=pl.sc_part.data_ptr(), tr_src=tr_src, tr_dst=tr_dst, n_tr=n_tr, stream=self.s)
+        self._enqueue_user_vectors_bwd(pl)
+        if pl.listwise_sum:
+            lib().call("amid_sum_vector_f32", pl.loss_part.data_ptr(), shp.B, pl.loss.data_ptr(), self.s)
+        return True
+
     def _head_io(self, pl: SasrecPlan, items: int, ditems: int):
         """What the one-launch heads (forward + loss + backward) read and write beside the parameters, under the header's names."""
         shp = pl.shape
@@ -1154,7 +1201,9 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             pl.wT16x3_written = False
         items = pl.xg.data_ptr() + 4 * 2 * shp.Mi * D
         ditems = pl.dxg.data_ptr() + 4 * 2 * shp.Mi * D
-        if (self.dr or self.itc_bs) and getattr(self, "_fuse_scorers", False):
+        if self._listwise_bwd(pl, items, ditems, tr_src, tr_dst, n_tr):
+            pass
+        elif (self.dr or self.itc_bs) and getattr(self, "_fuse_scorers", False):
             self._enqueue_scorers_fused(pl, items, ditems, tr_src, tr_dst, n_tr)
             self._enqueue_user_vectors_bwd(pl)
         elif self.dr:
@@ -1474,7 +1523,7 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
 
     def _enqueue_fwd_bwd(self, pl: SasrecPlan) -> None:
         """Forward (loss included; its sum rides in the gradient tail) + backward of a training step."""
-        self._fuse_head = self.FUSED_HEAD and not self.dr and not self.itc_bs
+        self._fuse_head = self.FUSED_HEAD and not self.dr and not self.itc_bs and self.loss == "bce"
         self._fuse_scorers = self.FUSED_HEAD and bool(self.dr or self.itc_bs) and (not self.dr or pl.shape.NI <= 16)
         # the step's own loss masks row b's terms of domain 1 - domain_id[b] with zero (train_sr.py:205-211; the doubly-robust
         # objectives likewise, train_sr_dr.py:216-221, :392-394): the encoder of that domain gets an all-zero gradient for row b.

@@ -137,7 +137,7 @@ class Bert4recEngine(SasrecEngine):
         """Whether this engine's train step on `pl` encodes the live sequences only (engine._enqueue_fwd_bwd): the plain head, no
         comp module in front of the encoders, the matrix-core attention kernel's shape."""
         shp = pl.shape
-        return bool(getattr(pl, "strip", False) and not self.comp and not self.dr and self.FUSED_HEAD and self.LIVE_FORWARD
+        return bool(getattr(pl, "strip", False) and not self.comp and not self.dr and self.FUSED_HEAD and self.LIVE_FORWARD and self.loss == "bce"
                     and lib().value("amid_attn_bert_live_supported", shp.Tenc, self.D, self.H))
 
     def __init__(self, *args, comp: str = "", comp_bs: int = 0, comp_threshold: float = 0.5, **kw):
@@ -223,6 +223,8 @@ class Bert4recEngine(SasrecEngine):
         else:
             self._enqueue_blocks_rowtile(pl, st, tr)
         items = pl.xg.data_ptr() + 4 * 2 * shp.Mi * D
+        if self._listwise_fwd(pl, with_loss, sum_loss):
+            return
         if self.dr:                                  # three heads (model_seq.py:301-305) on the plain means
             if getattr(self, "_fuse_scorers", False) and with_loss and not sum_loss:
                 self._enqueue_user_vectors(pl)       # the scorers run as ONE forward + loss + backward launch in enqueue_backward
@@ -478,7 +480,9 @@ class Bert4recEngine(SasrecEngine):
         pl.transposed_in_forward = False
         items = pl.xg.data_ptr() + 4 * 2 * shp.Mi * D
         ditems = pl.dxg.data_ptr() + 4 * 2 * shp.Mi * D
-        if self.dr and getattr(self, "_fuse_scorers", False):
+        if self._listwise_bwd(pl, items, ditems, None, None, 0):
+            pass
+        elif self.dr and getattr(self, "_fuse_scorers", False):
             self._enqueue_scorers_fused(pl, items, ditems, None, None, 0)
             self._enqueue_user_vectors_bwd(pl)
         elif self.dr:

@@ -47,6 +47,8 @@ class DataParallelMixin:
         parts, merge of the sparse parts, Adam): three or four host calls, and replicas that are bit-identical by construction; the
         pair of graphs is captured per distinct (umax, dense), so callers should pass a bucketed bound (bench.py: the pool's maximum).
         dense: "gather" | "allreduce" (default: DENSE_EXCHANGE)."""
+        if getattr(self, "loss", "bce") != "bce" and exchange is not None and exchange.world > 1:
+            raise ValueError(f"loss = {self.loss!r}: the data-parallel listwise step is not built (an exchange over {exchange.world} ranks)")
         inc_dp = bool(self.inc_bs and exchange.active)
         if inc_dp:
             # InnerComp under data parallel: bs is the GLOBAL batch, the plan a shard of it; the module's softmax / Linear(bs, 1) over the

@@ -100,6 +100,8 @@ class Gru4recEngine(SasrecEngine):
     def __init__(self, *args, **kw):
         if kw.get("compute", "f32") != "f32":
             raise ValueError("GRU4Rec: compute must be 'f32' (the recurrence runs on the fp32 matrix instructions only)")
+        if kw.get("loss", "bce") != "bce" and kw.get("itc_bs", 0):
+            raise ValueError(f"loss = {kw['loss']!r} is refused with GRU4Rec isItC: the listwise step is not built for it")
         super().__init__(*args, **kw)
 
     def _dense_names(self):
@@ -113,7 +115,8 @@ class Gru4recEngine(SasrecEngine):
 
     def live_forward_ok(self, pl) -> bool:
         """Whether this engine's train step on `pl` encodes the live sequences only (engine._enqueue_fwd_bwd)."""
-        return bool(getattr(pl, "strip", False) and not self.itc_bs and not self.dr and not self.inc_bs and self.FUSED_HEAD and self.LIVE_FORWARD)
+        return bool(getattr(pl, "strip", False) and not self.itc_bs and not self.dr and not self.inc_bs and self.FUSED_HEAD and self.LIVE_FORWARD
+                    and self.loss == "bce")
 
     # ---- data parallel: not built (the exchange would work unchanged; nothing here has been run at a world above one)
     def train_step_dp(self, pl, exchange, *args, **kw):
@@ -194,6 +197,8 @@ class Gru4recEngine(SasrecEngine):
             self._enqueue_k1(pl, None, None, None, 0, 0.0, lf)      # plain gather: no positional table, no embedding dropout, no "== 0" mask
         self._enqueue_encoders(pl, lf, save=pl.need_grad)
         items = pl.xg.data_ptr() + 4 * 2 * shp.Mi * D
+        if self._listwise_fwd(pl, with_loss, sum_loss):
+            return
         if (self.dr or self.itc_bs) and getattr(self, "_fuse_scorers", False) and with_loss and not sum_loss:
             self._enqueue_user_vectors(pl)           # train step: the scorers run as ONE forward + loss + backward launch in enqueue_backward
             return
@@ -221,7 +226,9 @@ class Gru4recEngine(SasrecEngine):
         fp = self.dense
         items = pl.xg.data_ptr() + 4 * 2 * shp.Mi * D
         ditems = pl.dxg.data_ptr() + 4 * 2 * shp.Mi * D
-        if (self.dr or self.itc_bs) and getattr(self, "_fuse_scorers", False):
+        if self._listwise_bwd(pl, items, ditems, None, None, 0):
+            pass
+        elif (self.dr or self.itc_bs) and getattr(self, "_fuse_scorers", False):
             self._enqueue_scorers_fused(pl, items, ditems, None, None, 0)
             self._enqueue_user_vectors_bwd(pl)
         elif self.dr:

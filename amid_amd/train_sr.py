@@ -8,7 +8,9 @@ loaders, five seeds 0..4, loss logged every 20 iterations, best-so-far HR/NDCG/M
 Additions: ``--data_root`` (the reference hard-codes /ossfs/workspace/CDSR), ``--seeds``, ``--device``,
 ``--no_graph``, ``--no_pool``, ``--max_steps``, ``--dtype {fp32,bf16}``, ``--neg_sampling {uniform,popularity}`` with ``--neg_power P``
 (0 .. 1, default 1.0) and ``--neg_sampling_for {both,train,eval}`` (negatives drawn in proportion to count ** P in the training CSV
-instead of uniformly: DESIGN.md section 16); data parallel when launched by ``python -m torch.distributed.run --nproc-per-node N``
+instead of uniformly: DESIGN.md section 16), ``--train_negs K`` (1 .. 1023 sampled negatives a training row, default 1) with
+``--loss {bce,softmax,bpr}`` (the objective over the row's positive and its K negatives; default the reference's masked BCE; softmax / bpr:
+one GPU, fp32, no --isInC: DESIGN.md section 17); data parallel when launched by ``python -m torch.distributed.run --nproc-per-node N``
 (one process per GPU, RCCL, ``--bs`` per GPU; BASELINE.json configs[3]).
 
     python train_sr.py --data_root /path/to/AMID -ds amazon -dm cloth_sport --overlap_ratio 0.75 \
@@ -96,6 +98,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--neg_sampling_for", type=str, default="both", choices=("both", "train", "eval"), action=_NegFlag,
                    help="--neg_sampling popularity: which loaders draw that way (the others stay uniform)")
     p.set_defaults(neg_flags_given=())
+    p.add_argument("--train_negs", type=int, default=1, metavar="K", help="sampled negatives per training row, 1 .. 1023 (the reference: 1)")
+    p.add_argument("--loss", type=str, default="bce", choices=("bce", "softmax", "bpr"),
+                   help="the training objective over a row's positive and its --train_negs negatives: the reference's masked BCE, sampled "
+                        "softmax, or BPR (the validation loss stays the BCE)")
     p.add_argument("--save_dir", type=str, default=None,
                    help="write DIR/seed{i}/best_d1.pt and best_d2.pt (weights only, kept when MRR_d1 / MRR_d2 >= the best so far; held as "
                         "device copies until the seed's run ends: two extra table-sized buffers in HBM) and DIR/seed{i}/last.pt (the "
@@ -107,10 +113,10 @@ def build_parser() -> argparse.ArgumentParser:
 
 # what a last.pt must share with the command line that resumes it
 RESUME_KEYS = ("model", "emb_dim", "seq_len", "hid_dim", "isItC", "isInC", "dtype", "dataset_type", "domain_type", "bs", "overlap_ratio",
-               "neg_sampling", "neg_power", "neg_sampling_for")
+               "neg_sampling", "neg_power", "neg_sampling_for", "train_negs", "loss")
 _FLAGS = {"dataset_type": "-ds", "domain_type": "-dm"}
 # what a last.pt written before a key existed counts as
-_RESUME_DEFAULTS = {"neg_sampling": "uniform", "neg_power": 1.0, "neg_sampling_for": "both"}
+_RESUME_DEFAULTS = {"neg_sampling": "uniform", "neg_power": 1.0, "neg_sampling_for": "both", "train_negs": 1, "loss": "bce"}
 
 
 def check_neg_sampling(args) -> None:
@@ -119,6 +125,16 @@ def check_neg_sampling(args) -> None:
         raise SystemExit(f"{args.neg_flags_given[0]} belongs to --neg_sampling popularity")
     if not 0.0 <= args.neg_power <= 1.0:
         raise SystemExit(f"--neg_power must be in 0..1, got {args.neg_power}")
+
+
+def check_train_loss(args) -> None:
+    """--train_negs / --loss against the other flags: SystemExit before any GPU work."""
+    if not 1 <= args.train_negs <= 1023:
+        raise SystemExit(f"--train_negs must be in 1..1023, got {args.train_negs}")
+    if args.loss != "bce" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"--loss {args.loss} trains on one GPU: the data-parallel listwise step is not built")
+    if args.loss != "bce" and args.dtype == "bf16":
+        raise SystemExit(f"--loss {args.loss} runs in fp32: --dtype bf16 is not built for it")
 
 
 def neg_loader_args(args, role: str, ds=None, ds_train=None) -> dict:
@@ -399,6 +415,7 @@ def init_data_parallel(args):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_neg_sampling(args)
+    check_train_loss(args)
     ck = read_resume(args)
     rank, world = init_data_parallel(args)
     summary = list(ck["extra"]["summary"]) if ck is not None else []
@@ -426,7 +443,7 @@ def main(argv=None):
                 ds_train.shift_items(item_length + 2)
                 ds_val.shift_items(item_length + 2)
             trains.append(DeviceBatches(ds_train, args.bs, shuffle=True, device=args.device, seed=i, rank=rank, world=world,
-                                        **neg_loader_args(args, "train")))
+                                        train_negs=args.train_negs, **neg_loader_args(args, "train")))
             # (isItC under data parallel: InterComp's Linear(bs, 1) is built for the GLOBAL batch of world x --bs rows, so the
             # evaluation, which every rank runs whole, steps through batches of that size)
             vals.append(DeviceBatches(ds_val, args.bs * (world if (args.isItC or args.isInC) else 1), shuffle=False, device=args.device, seed=i,
@@ -454,13 +471,14 @@ def main(argv=None):
         model = cls(user_length=user_length, user_emb_dim=args.emb_dim, item_length=item_length, item_emb_dim=args.emb_dim,
                     seq_len=args.seq_len, hid_dim=args.hid_dim, bs=args.bs * (world if (args.isItC or args.isInC) else 1), isInC=args.isInC, isItC=args.isItC,
                     threshold1=args.ts1,
-                    threshold2=args.ts2, lr=args.lr, seed=i, **({"compute": "bf16"} if args.dtype == "bf16" else {}))
+                    threshold2=args.ts2, lr=args.lr, seed=i, **({"compute": "bf16"} if args.dtype == "bf16" else {}),
+                    **({"loss": args.loss} if args.loss != "bce" else {}))
         exchange = None
         if world > 1:
             # identical replicas (weights from seed i on every rank), but each rank's own dropout stream
             model.engine.set_step(model.engine.step, seed=model.engine.rank_seed(i, rank))
             from .dist import SparseDenseExchange
-            n_idx = args.bs * (2 * args.seq_len + 2)                                      # per-rank index count of a train batch (1 negative)
+            n_idx = args.bs * (2 * args.seq_len + 1 + args.train_negs)                    # per-rank index count of a train batch
             exchange = SparseDenseExchange(model.engine.merge_backend(world * n_idx),
                                            host_staging=os.environ.get("AMID_DIST_BACKEND", "nccl") != "nccl")
         files = RunFiles(args, i, model, {"train": train_batches, "val": val_batches}, summary)

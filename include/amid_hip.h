@@ -456,6 +456,23 @@ int amid_scorer_multi_fwd_bwd_f32(const float* u, const float* items, const floa
                                   float* loss_part, float* dr_loss_part, float* du, float* ditems, float* const* sc_part,
                                   const float* const* tr_src, float* const* tr_dst, int n_tr, void* stream);
 
+/* The scorer of a train step under a LISTWISE objective on K = NI - 1 sampled negatives, ONE launch (csrc/head_listwise.hip): scorer
+ * forward over row b's candidates items [B, NI, D] (column 0 the positive, dataset_seq.py:191,199; no labels are read) on given user
+ * vectors u [2, B, D], the row's objective on the LOGITS z of its own domain (domain_id[b] != 0; the other domain is masked out,
+ * train_sr.py:205-211), scorer backward from dLoss/dz -- no division by p (1 - p) anywhere, so a saturated p = 1.0f stays finite.
+ *   kind 1 (sampled softmax): L_b = logsumexp_n z[n] - z[0];                     dz[n] = exp(z[n] - lse) - [n == 0]
+ *   kind 2 (BPR):             L_b = mean_{n >= 1} softplus(z[n] - z[0]);         dz[n] = sigmoid(z[n] - z[0]) / K, dz[0] = -sum_{n >= 1} dz[n]
+ * loss_part[b] = L_b / B and dz is scaled by 1 / B; every sum runs in a fixed order (the kernel's comment).  Outputs: p1 / p2 [B, NI]
+ * (sigmoid(z): the bits of amid_scorer_fwd_f32), dz1 / dz2 [B, NI] (the other domain's exactly 0), du [2, B, D] (the other domain's
+ * half exactly 0), ditems [B, NI, D], sc_part (per-row partials of dW1, db1, dW2, db2 as amid_scorer_bwd_f32).  tr_*: as
+ * amid_head_bwd_f32.  AMID_ERR_ARG: a null pointer (tr_src / tr_dst may be null with n_tr 0), kind outside {1, 2}, NI < 2, B or D <= 0,
+ * n_tr outside 0 .. 32; AMID_ERR_UNSUPPORTED: NI > 1024, D > 128, D % 32 != 0, hid outside 4 .. 64 or hid % 4 != 0 -- all before
+ * anything touches a device. */
+int amid_scorer_listwise_fwd_bwd_f32(const float* u, const float* items, const float* w1, const float* b1, const float* w2,
+                                     const float* b2, const long long* domain_id, int kind, int B, int NI, int D, int hid,
+                                     float* p1, float* p2, float* dz1, float* dz2, float* loss_part, float* du, float* ditems,
+                                     float* sc_part, const float* const* tr_src, float* const* tr_dst, int n_tr, void* stream);
+
 /* ---- InnerComp on the SASRec path (isInC; next-1 of SURVEY.md 8(f)) -------------------------------------------------------
  * replaces: InnerComp.forward model_seq.py:459-472 as used at model_seq.py:422-424 (on the gathered rows, before the encoders,
  * which then run over 2T tokens with 2T-row pos_emb tables, :398-401) and its autograd.  Compute-once form (csrc/innercomp.hip):
