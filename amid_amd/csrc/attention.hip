@@ -307,10 +307,12 @@ int amid_attn_long_bwd_launch(const void* args, void* stream);
 static bool long_shape(const AttnArgs& a) {
     return a.causal && a.key_keep == nullptr && a.D / a.H == 16 && a.T > 64 && a.T <= 256 && a.H <= 8 && a.H % 4 == 0;
 }
-// attention_mfma_bert.hip: matrix-core kernels for the bidirectional head-dim-32 T <= 64 case (key mask optional)
+// attention_mfma_bert.hip: matrix-core kernels for the bidirectional head-dim-32 T <= 64 case (key mask optional), up to four heads:
+// two forward waves per head and H * BERT_BWD_LDS_PER_WAVE <= 44 KiB of backward LDS.  More heads of 32 (D 160 .. 256) take the
+// general kernels below, which raise their LDS limit themselves
 int amid_attn_bert_fwd_launch(const void* args, void* stream);
 int amid_attn_bert_bwd_launch(const void* args, void* stream);
-static bool bert_shape(const AttnArgs& a) { return !a.causal && a.D / a.H == 32 && a.T <= 64 && a.H <= 8; }
+static bool bert_shape(const AttnArgs& a) { return !a.causal && a.D / a.H == 32 && a.T <= 64 && a.H <= 4; }
 
 // LDS of one workgroup that serves H / hg heads (their D / hg columns of K / V, then of Q / dO)
 static size_t attn_fwd_lds(int T, int D, int hg) { return (size_t)2 * T * (D / hg) * sizeof(float); }

@@ -19,7 +19,7 @@ __device__ __forceinline__ int bert_live_seq(const AttnArgs& a, int j) {
     return (j >= n0 ? a.B : 0) + a.live[j];
 }
 
-template <int WPH>                                         // waves per head: 2 (H <= 4: eight waves per sequence) or 1
+template <int WPH>                                         // waves per head: 2 (H <= 4: eight waves per sequence) is the one launched; 1 is not
 __global__ __launch_bounds__(512) void attn_fwd_bert_kernel(const AttnArgs a) {
     constexpr int TPW = 4 / WPH;                           // query tiles per wave
     const int T = a.T, D = a.D, H = a.H;
@@ -237,15 +237,16 @@ using namespace amid;
 // called by the entry points in attention.hip when the shape fits (bidirectional, head dim 32, T <= 64)
 int amid_attn_bert_fwd_launch(const void* args, void* stream) {
     const AttnArgs& a = *(const AttnArgs*)args;
-    const size_t lds = (size_t)(a.H <= 4 ? 2 : 1) * a.H * ATTN_BWD_TILE_FLOATS * sizeof(float);      // a transpose tile per wave
-    if (a.H <= 4) attn_fwd_bert_kernel<2><<<a.live != nullptr ? a.B : 2 * a.B, 2 * a.H * 64, lds, (hipStream_t)stream>>>(a);
-    else attn_fwd_bert_kernel<1><<<a.live != nullptr ? a.B : 2 * a.B, a.H * 64, lds, (hipStream_t)stream>>>(a);
+    if (a.H > 4) return AMID_ERR_UNSUPPORTED;                  // (bert_shape, attention.hip: two waves per head, at most eight per workgroup)
+    const size_t lds = (size_t)2 * a.H * ATTN_BWD_TILE_FLOATS * sizeof(float);      // a transpose tile per wave
+    attn_fwd_bert_kernel<2><<<a.live != nullptr ? a.B : 2 * a.B, 2 * a.H * 64, lds, (hipStream_t)stream>>>(a);
     AMID_LAUNCH_CHECK();
     return AMID_OK;
 }
 
 int amid_attn_bert_bwd_launch(const void* args, void* stream) {
     const AttnArgs& a = *(const AttnArgs*)args;
+    if (a.H > 4) return AMID_ERR_UNSUPPORTED;                  // (H * BERT_BWD_LDS_PER_WAVE stays under the 64 KiB a launch gets unasked)
     const size_t lds = (size_t)a.H * BERT_BWD_LDS_PER_WAVE;
     attn_bwd_bert_kernel<<<a.live != nullptr ? a.B : 2 * a.B, a.H * 64, lds, (hipStream_t)stream>>>(a);
     AMID_LAUNCH_CHECK();

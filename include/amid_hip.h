@@ -252,7 +252,8 @@ int amid_sas_oproj_ffn_qkv_fwd_f32(const float* o, const float* qn, const float*
  * Attention.forward of BERT4Rec (model_seq.py:149-162, causal=0 with key_keep [B,T] from seq_d2 > 0, :288).
  * stats: [2M, H, 2] (row max, 1/row sum) saved for backward.  Causal, T <= 64, H <= 8, head dim 16 or 8 (D = 64 with the reference's 8
  * heads, train_sr.py:364: a 16-column tile is then a PAIR of heads) run on the matrix cores (csrc/attention_mfma.h); 64 < T <= 256 at head
- * dim 16 their blocked form; BERT4Rec's shape its own matrix-core kernels; everything else the general VALU kernels. */
+ * dim 16 their blocked form; BERT4Rec's shape (bidirectional, head dim 32, T <= 64, H <= 4) its own matrix-core kernels; everything else
+ * the general VALU kernels. */
 int amid_attn_fwd_f32(const float* q, const float* k, const float* v, const unsigned char* key_keep, int B, int T, int D, int H, int causal,
                       int layer, const void* step_state, int train, float p_drop, float* o, float* stats, void* stream);
 int amid_attn_bwd_f32(const float* q, const float* k, const float* v, const float* o, const float* stats, const float* d_o,
