@@ -85,12 +85,15 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
 
     def __init__(self, item_length: int, emb_dim: int, seq_len: int, hid_dim: int, device="cuda:0", lr: float = 5e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0, itc_bs: int = 0, itc_threshold: float = 0.5, dr: bool = False,
-                 dr_e_w: float = 0.1, compute: str = "f32", inc_bs: int = 0, inc_threshold: float = 0.5, loss: str = "bce"):
+                 dr_e_w: float = 0.1, compute: str = "f32", inc_bs: int = 0, inc_threshold: float = 0.5, loss: str = "bce",
+                 hard_negs: int = 0, hard_skip: int = 0):
         """itc_bs > 0: SASRec(isItC=True, bs=itc_bs, threshold2=itc_threshold) -- InterComp after the encoders
         (model_seq.py:426-431); every batch must then hold exactly itc_bs rows (trans_bs is Linear(bs, 1) over the batch).
         loss: the objective of a train step over a row's candidates (column 0 the positive): "bce" the reference's masked BCE
         (train_sr.py:203-212), "softmax" / "bpr" sampled softmax / BPR on the own domain's logits (csrc/head_listwise.hip; DESIGN.md
-        section 17).  Evaluation (test(), eval_ranks, recommend*) does not depend on it."""
+        section 17).  Evaluation (test(), eval_ranks, recommend*) does not depend on it.
+        hard_negs = H > 0 (with loss "softmax" / "bpr"): of a row's sampled negatives only the H ranked hard_skip .. hard_skip + H - 1 by the
+        current model's own-domain logit enter the objective and the backward (csrc/head_mined.hip); 0: all of them."""
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
         if loss != "bce":
@@ -100,6 +103,14 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             if why:
                 raise ValueError(f"loss = {loss!r} is refused with {why}")
         self.loss = loss
+        hard_negs, hard_skip = int(hard_negs), int(hard_skip)
+        if hard_negs < 0 or hard_skip < 0:
+            raise ValueError(f"hard_negs and hard_skip must be >= 0, got {hard_negs} and {hard_skip}")
+        if hard_negs > 0 and loss == "bce":
+            raise ValueError(f"hard_negs = {hard_negs} needs loss 'softmax' or 'bpr': the masked BCE has one negative a row, nothing to mine")
+        if hard_skip > 0 and hard_negs == 0:
+            raise ValueError(f"hard_skip = {hard_skip} without hard_negs: there is no mined list to skip the top of")
+        self.hard_negs, self.hard_skip = hard_negs, hard_skip
         L = lib()        # raises AmidLibraryError when the HIP library is missing: no fallback
         if self.SEQ_FWD_VARIANT:          # A/B measurements of the fused forward's builds (amid_sas_seq_fwd_variant)
             L.value("amid_sas_seq_fwd_variant", int(self.SEQ_FWD_VARIANT))
@@ -1149,6 +1160,8 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             raise ValueError(f"loss = {self.loss!r}: the listwise step is single-GPU (a data-parallel shard of a comp batch is refused)")
         if pl.shape.NI < 2 or pl.shape.NI > 1024:
             raise ValueError(f"loss = {self.loss!r} needs 1 .. 1023 negatives a row, got {pl.shape.NI - 1}")
+        if self.hard_negs and self.hard_skip + self.hard_negs > pl.shape.NI - 1:
+            raise ValueError(f"hard_skip + hard_negs = {self.hard_skip} + {self.hard_negs} exceeds the {pl.shape.NI - 1} negatives of a row")
         self._enqueue_user_vectors(pl)
         pl.listwise_owed, pl.listwise_sum = True, bool(sum_loss)
         return True
@@ -1159,10 +1172,15 @@ class SasrecEngine(InputMixin, GraphMixin, DataParallelMixin, TopkMixin):
             return False
         pl.listwise_owed = False
         shp = pl.shape
-        lib().call_named("amid_scorer_listwise_fwd_bwd_f32", self._scorer(), u=pl.u.data_ptr(), items=items, domain_id=pl.domain.data_ptr(),
-                         kind=LOSSES.index(self.loss), B=shp.B, NI=shp.NI, D=self.D, hid=self.hid, p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(),
-                         dz1=pl.dp1.data_ptr(), dz2=pl.dp2.data_ptr(), loss_part=pl.loss_part.data_ptr(), du=pl.du.data_ptr(), ditems=ditems,
-                         sc_part=pl.sc_part.data_ptr(), tr_src=tr_src, tr_dst=tr_dst, n_tr=n_tr, stream=self.s)
+        io = dict(u=pl.u.data_ptr(), items=items, domain_id=pl.domain.data_ptr(), kind=LOSSES.index(self.loss), B=shp.B, NI=shp.NI, D=self.D,
+                  hid=self.hid, p1=pl.p1.data_ptr(), p2=pl.p2.data_ptr(), dz1=pl.dp1.data_ptr(), dz2=pl.dp2.data_ptr(),
+                  loss_part=pl.loss_part.data_ptr(), du=pl.du.data_ptr(), ditems=ditems, sc_part=pl.sc_part.data_ptr(), tr_src=tr_src,
+                  tr_dst=tr_dst, n_tr=n_tr, stream=self.s)
+        if self.hard_negs:          # the mined list: pl.sel [B, H] the kept positions, pl.z [B, NI] the own domain's logits (section 18)
+            lib().call_named("amid_scorer_mined_fwd_bwd_f32", self._scorer(), io, keep=self.hard_negs, skip=self.hard_skip,
+                             sel=pl.sel.data_ptr(), z=pl.z.data_ptr())
+        else:
+            lib().call_named("amid_scorer_listwise_fwd_bwd_f32", self._scorer(), io)
         self._enqueue_user_vectors_bwd(pl)
         if pl.listwise_sum:
             lib().call("amid_sum_vector_f32", pl.loss_part.data_ptr(), shp.B, pl.loss.data_ptr(), self.s)

@@ -153,12 +153,15 @@ class SASRec(nn.Module):
     COMP_IN_FRONT = False        # InterComp after the encoders (model_seq.py:426-431), the configuration run.sh trains
 
     def __init__(self, user_length, user_emb_dim, item_length, item_emb_dim, seq_len, hid_dim, bs, isInC, isItC, threshold1,
-                 threshold2, isDR=False, device: Optional[str] = None, lr: float = 5e-4, seed: int = 0, compute: str = "f32", loss: str = "bce"):
+                 threshold2, isDR=False, device: Optional[str] = None, lr: float = 5e-4, seed: int = 0, compute: str = "f32", loss: str = "bce",
+                 hard_negs: int = 0, hard_skip: int = 0):
         """Beyond the reference's arguments: device, lr / seed (the fused train_step owns Adam and the dropout counter),
         compute ("f32": exact fp32 matrix products, the default; "bf16": bf16 MFMA operands with fp32 accumulation, SASRec with
         emb_dim 128 only -- BASELINE.json configs[2]) and loss ("bce": the reference's masked BCE, the default; "softmax" / "bpr":
         sampled softmax / BPR of a fused train step over the row's positive, column 0, and its sampled negatives -- refused with
-        isDR, isInC, compute "bf16" and data parallel; evaluation and the autograd path are unchanged)."""
+        isDR, isInC, compute "bf16" and data parallel; evaluation and the autograd path are unchanged) with hard_negs / hard_skip (H > 0:
+        the step trains on the H of the sampled negatives that the current model ranks hard_skip .. hard_skip + H - 1 by logit, DESIGN.md
+        section 18; needs loss "softmax" / "bpr")."""
         super().__init__()
         if isInC and isItC and self.COMP_IN_FRONT:
             raise ValueError("BERT4Rec(isInC=True, isItC=True): the reference itself fails on this combination (its key mask keeps 2T "
@@ -184,6 +187,8 @@ class SASRec(nn.Module):
             kw["compute"] = compute
         if loss != "bce":
             kw["loss"] = loss
+        if hard_negs or hard_skip:
+            kw.update(hard_negs=hard_negs, hard_skip=hard_skip)
         self.engine = self.ENGINE_CLS(item_length, item_emb_dim, seq_len, hid_dim, device=dev, lr=lr, seed=seed, **kw)
         eng = self.engine
         self._param_names = ["item_emb_layer.emb_item.weight"] + list(eng.dense.slots)

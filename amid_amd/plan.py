@@ -256,6 +256,9 @@ class SasrecPlan:
         self._alloc_model_bwd(eng, f)
         self.sc_P = L.value("amid_scorer_part_floats", D, hid)
         self.sc_part = f(B, self.sc_P)
+        if getattr(eng, "hard_negs", 0):          # hard-negative mining (csrc/head_mined.hip): the kept positions and the own domain's logits
+            self.sel = torch.zeros(B, eng.hard_negs, dtype=torch.int32, device=dev)
+            self.z = f(B, NI)
         if dr:
             self.sc_part_ips, self.sc_part_g = f(B, self.sc_P), f(B, self.sc_P)
         # sparse side

@@ -10,7 +10,8 @@ Additions: ``--data_root`` (the reference hard-codes /ossfs/workspace/CDSR), ``-
 (0 .. 1, default 1.0) and ``--neg_sampling_for {both,train,eval}`` (negatives drawn in proportion to count ** P in the training CSV
 instead of uniformly: DESIGN.md section 16), ``--train_negs K`` (1 .. 1023 sampled negatives a training row, default 1) with
 ``--loss {bce,softmax,bpr}`` (the objective over the row's positive and its K negatives; default the reference's masked BCE; softmax / bpr:
-one GPU, fp32, no --isInC: DESIGN.md section 17); data parallel when launched by ``python -m torch.distributed.run --nproc-per-node N``
+one GPU, fp32, no --isInC: DESIGN.md section 17), ``--hard_negs H`` with ``--hard_skip S`` (train on the H of the K drawn negatives that the current
+model ranks S .. S + H - 1 by logit: DESIGN.md section 18); data parallel when launched by ``python -m torch.distributed.run --nproc-per-node N``
 (one process per GPU, RCCL, ``--bs`` per GPU; BASELINE.json configs[3]).
 
     python train_sr.py --data_root /path/to/AMID -ds amazon -dm cloth_sport --overlap_ratio 0.75 \
@@ -102,6 +103,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loss", type=str, default="bce", choices=("bce", "softmax", "bpr"),
                    help="the training objective over a row's positive and its --train_negs negatives: the reference's masked BCE, sampled "
                         "softmax, or BPR (the validation loss stays the BCE)")
+    p.add_argument("--hard_negs", type=int, default=0, metavar="H",
+                   help="with --loss softmax | bpr: train on the H hardest (highest-scoring under the current model) of the --train_negs drawn "
+                        "negatives a row (0: on all of them)")
+    p.add_argument("--hard_skip", type=int, default=0, metavar="S",
+                   help="with --hard_negs: leave out the S highest-scoring negatives (often false negatives) and keep the H after them")
     p.add_argument("--save_dir", type=str, default=None,
                    help="write DIR/seed{i}/best_d1.pt and best_d2.pt (weights only, kept when MRR_d1 / MRR_d2 >= the best so far; held as "
                         "device copies until the seed's run ends: two extra table-sized buffers in HBM) and DIR/seed{i}/last.pt (the "
@@ -113,10 +119,11 @@ def build_parser() -> argparse.ArgumentParser:
 
 # what a last.pt must share with the command line that resumes it
 RESUME_KEYS = ("model", "emb_dim", "seq_len", "hid_dim", "isItC", "isInC", "dtype", "dataset_type", "domain_type", "bs", "overlap_ratio",
-               "neg_sampling", "neg_power", "neg_sampling_for", "train_negs", "loss")
+               "neg_sampling", "neg_power", "neg_sampling_for", "train_negs", "loss", "hard_negs", "hard_skip")
 _FLAGS = {"dataset_type": "-ds", "domain_type": "-dm"}
 # what a last.pt written before a key existed counts as
-_RESUME_DEFAULTS = {"neg_sampling": "uniform", "neg_power": 1.0, "neg_sampling_for": "both", "train_negs": 1, "loss": "bce"}
+_RESUME_DEFAULTS = {"neg_sampling": "uniform", "neg_power": 1.0, "neg_sampling_for": "both", "train_negs": 1, "loss": "bce",
+                    "hard_negs": 0, "hard_skip": 0}
 
 
 def check_neg_sampling(args) -> None:
@@ -128,13 +135,21 @@ def check_neg_sampling(args) -> None:
 
 
 def check_train_loss(args) -> None:
-    """--train_negs / --loss against the other flags: SystemExit before any GPU work."""
+    """--train_negs / --loss / --hard_negs / --hard_skip against the other flags: SystemExit before any GPU work."""
     if not 1 <= args.train_negs <= 1023:
         raise SystemExit(f"--train_negs must be in 1..1023, got {args.train_negs}")
     if args.loss != "bce" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit(f"--loss {args.loss} trains on one GPU: the data-parallel listwise step is not built")
     if args.loss != "bce" and args.dtype == "bf16":
         raise SystemExit(f"--loss {args.loss} runs in fp32: --dtype bf16 is not built for it")
+    if args.hard_negs < 0 or args.hard_skip < 0:
+        raise SystemExit(f"--hard_negs and --hard_skip must be >= 0, got {args.hard_negs} and {args.hard_skip}")
+    if args.hard_negs > 0 and args.loss == "bce":
+        raise SystemExit("--hard_negs needs --loss softmax or bpr: the masked BCE has nothing to mine")
+    if args.hard_skip > 0 and args.hard_negs == 0:
+        raise SystemExit("--hard_skip belongs to --hard_negs")
+    if args.hard_skip + args.hard_negs > args.train_negs:
+        raise SystemExit(f"--hard_skip + --hard_negs = {args.hard_skip + args.hard_negs} exceeds the --train_negs {args.train_negs} drawn a row")
 
 
 def neg_loader_args(args, role: str, ds=None, ds_train=None) -> dict:
@@ -320,6 +335,21 @@ def test(model, args, val_batches):
     return out
 
 
+def mined_logit_means(model):
+    """With --hard_negs: the mean own-domain logit of the kept and of the other sampled negatives in the last step's plan (pl.z / pl.sel
+    as the step left them; one small reduction after the epoch's steps, nothing inside a step).  None without mining."""
+    pl = getattr(model, "_last_plan", None)
+    if pl is None or getattr(pl, "sel", None) is None or not getattr(model.engine, "hard_negs", 0):
+        return None
+    z, sel = pl.z, pl.sel.long()
+    kept = torch.zeros_like(z, dtype=torch.bool).scatter_(1, sel, True)
+    neg = z[:, 1:]
+    k = kept[:, 1:]
+    n_other = int(neg.shape[1] - sel.shape[1])
+    mean_kept = float(neg[k].mean())
+    return mean_kept, (float(neg[~k].mean()) if n_other > 0 else float("nan"))
+
+
 def train(model, train_batches, args, val_batches, exchange=None, start_epoch: int = 0, best=None, files=None):
     """train_sr.py:130-355 with the loop body (:190-217) fused into model.train_step.  start_epoch / best: where a resumed run goes on
     (RunFiles.resume); files: the RunFiles of --save_dir."""
@@ -372,6 +402,9 @@ def train(model, train_batches, args, val_batches, exchange=None, start_epoch: i
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         logger.info(f"epoch {epoch}: {n_samples} samples in {dt:.4f} s = {n_samples / dt:.0f} samples/s (loader included)")
+        mined = mined_logit_means(model)
+        if mined is not None:
+            logger.info(f"epoch {epoch}: hard negatives, last step: mean logit kept {mined[0]:.4f} \tnot kept {mined[1]:.4f}")
         t1 = time.perf_counter()
         res = test(model, args, val_batches)
         if files is not None:
@@ -472,7 +505,8 @@ def main(argv=None):
                     seq_len=args.seq_len, hid_dim=args.hid_dim, bs=args.bs * (world if (args.isItC or args.isInC) else 1), isInC=args.isInC, isItC=args.isItC,
                     threshold1=args.ts1,
                     threshold2=args.ts2, lr=args.lr, seed=i, **({"compute": "bf16"} if args.dtype == "bf16" else {}),
-                    **({"loss": args.loss} if args.loss != "bce" else {}))
+                    **({"loss": args.loss} if args.loss != "bce" else {}),
+                    **({"hard_negs": args.hard_negs, "hard_skip": args.hard_skip} if args.hard_negs else {}))
         exchange = None
         if world > 1:
             # identical replicas (weights from seed i on every rank), but each rank's own dropout stream

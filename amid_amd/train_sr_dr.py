@@ -130,9 +130,9 @@ def main(argv=None):
     if not args.isDR:
         raise SystemExit("train_sr_dr.py trains the doubly-robust heads (the reference's loop unpacks six outputs, train_sr_dr.py:204); "
                          "use train_sr.py without them")
-    if args.loss != "bce" or args.train_negs != 1:
+    if args.loss != "bce" or args.train_negs != 1 or args.hard_negs or args.hard_skip:
         raise SystemExit("train_sr_dr.py: the doubly-robust objectives are written on the BCE value of one negative a row "
-                         "(--loss bce, --train_negs 1)")
+                         "(--loss bce, --train_negs 1, no --hard_negs / --hard_skip)")
     classes = {"sasrec": SASRec, "bert4rec": BERT4Rec, "gru4rec": GRU4RecAMID}
     if args.model.lower() not in classes:
         raise SystemExit(f"unknown --model {args.model!r} (gru4rec | sasrec | bert4rec)")

@@ -474,6 +474,23 @@ int amid_scorer_listwise_fwd_bwd_f32(const float* u, const float* items, const f
                                      float* p1, float* p2, float* dz1, float* dz2, float* loss_part, float* du, float* ditems,
                                      float* sc_part, const float* const* tr_src, float* const* tr_dst, int n_tr, void* stream);
 
+/* amid_scorer_listwise_fwd_bwd_f32 with HARD-NEGATIVE MINING, still one launch (csrc/head_mined.hip): the forward
+ * runs over all NI candidates; of row b's M = NI - 1 negatives, ranked by their own-domain logit
+ *   rank(n) = #{ j in 1 .. M : z[j] > z[n] or (z[j] == z[n] and j < n) }      (a higher logit first, ties to the lower position),
+ * those with skip <= rank(n) < skip + keep are kept; the objective is the listwise one on the compact list c = [0] + kept positions in
+ * ascending order (NI -> 1 + keep; BPR's 1 / K is 1 / keep), summed in the listwise launch's order over list entries, and the scorer
+ * backward runs over that list only.  The selection is a constant for differentiation.  Outputs beside the listwise launch's: sel
+ * [B, keep] (the kept positions, ascending) and z [B, NI] (the own domain's logits).  dz of the own domain is dLoss/dz / B at column 0 and
+ * the kept positions and exactly 0 elsewhere, ditems[b, n, :] is written as exactly 0 for every n not kept; du, sc_part and the kept
+ * ditems rows are the backward over the list.  At keep = NI - 1, skip = 0: p1 / p2, z, loss_part and dz are the listwise launch's bits.
+ * Inputs are finite.  AMID_ERR_ARG: keep < 1, skip < 0, skip + keep > NI - 1, a null sel or z, and the listwise entry's; then
+ * AMID_ERR_UNSUPPORTED as the listwise entry -- all before anything touches a device. */
+int amid_scorer_mined_fwd_bwd_f32(const float* u, const float* items, const float* w1, const float* b1, const float* w2,
+                                  const float* b2, const long long* domain_id, int kind, int keep, int skip, int B, int NI, int D,
+                                  int hid, float* p1, float* p2, float* dz1, float* dz2, float* loss_part, float* du, float* ditems,
+                                  float* sc_part, int* sel, float* z, const float* const* tr_src, float* const* tr_dst, int n_tr,
+                                  void* stream);
+
 /* ---- InnerComp on the SASRec path (isInC; next-1 of SURVEY.md 8(f)) -------------------------------------------------------
  * replaces: InnerComp.forward model_seq.py:459-472 as used at model_seq.py:422-424 (on the gathered rows, before the encoders,
  * which then run over 2T tokens with 2T-row pos_emb tables, :398-401) and its autograd.  Compute-once form (csrc/innercomp.hip):
